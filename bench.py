@@ -15,9 +15,13 @@ the batch, with the per-date forecast tables already resident in HBM:
   default; --strategy direct: k_direct) -> [all-gather] -> finalise.
   (--strategy prefix: k_tables -> joint-mass row prefixes k_mass -> k_solve_prefix.)
 
-Prints ONE JSON line (rank 0).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps of the
+in-flight leg and prints the headline figures; `--dump-outputs DIR` also writes what the last
+timed step computed.  Everything below that takes runs of its own (single_solve, roofline,
+e2e, cpu_baseline, other_configs) is measured only with `--full`.
   value        -- whole-job VaR-dates/s with `--inflight` independent batches in flight
                   (each its own plan + HIP stream; default 3), K timed steps.
+  ms_per_step  -- wall milliseconds per timed step of that leg.
   single_solve -- the SURVEY.md §8(d) figure: T / wall time of ONE calc_var-equivalent
                   solve (utils/calc_var_class.py:109-175), one batch at a time, K steps.
   roofline     -- dominant kernel (k_compact / k_sorted / k_mass), bound "fp64-valu":
@@ -73,7 +77,7 @@ def parse():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="process group for N > 1 (nccl = RCCL over xGMI; gloo: the multi-rank path on "
                          "fewer GPUs than ranks, ranks sharing devices round-robin -- a test rehearsal)")
-    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--steps", type=int, default=100, help="timed steps of the in-flight leg (and of each --full leg)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", type=int, default=2, help="BASELINE config number (1-5)")
     ap.add_argument("--dates-per-gpu", type=int, default=None)
@@ -101,6 +105,14 @@ def parse():
                          "main config is 2")
     ap.add_argument("--time-all", type=int, default=0,
                     help="HIP-event time every kernel kind (adds event records to the timed region)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what takes runs of its own: the single solve, the "
+                         "dominant kernel's roofline, end to end, the CPU baseline and the other configs "
+                         "(each still switched by its own option)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float64): var, the VaR "
+                         "vector the step left in its output buffer, and iterations, the solve's bisection "
+                         "iteration count (rank 0)")
     return ap.parse_args()
 
 
@@ -276,105 +288,138 @@ def main():
     vals = (vars_[0] if not sharded else shardeds[0].var).cpu().numpy()
     ms_step = elapsed / a.steps * 1e3
     value = T_total * a.steps / elapsed
-    # one batch at a time; its back-to-back launches bracketed by two HIP events on the stream
-    # (the step is the one fused solve kernel for COMPACT / SORTED / SWEEP: the bracket over
-    # K steps / K is the kernel's average duration, as rocprofv3's kernel trace gives it)
-    one_kernel = a.strategy in ("compact", "sorted", "sweep") and not sharded
-    brk = []
-    if nf > 1 and a.single:
-        el1, _ = timed(1, a.steps, a.warmup, None, brk)
-        v1 = (vars_[0] if not sharded else shardeds[0].var).cpu().numpy()
-        assert np.array_equal(v1, vals, equal_nan=True), "single-solve leg changed the VaR"
-    else:
-        el1 = elapsed
-        brk = brk0
-    single = {"value": T_total * a.steps / el1, "unit": "VaR-dates/s", "ms_per_step": el1 / a.steps * 1e3,
-              "inflight": 1, "steps": a.steps,
-              "scope": "one calc_var-equivalent solve per step (utils/calc_var_class.py:109-175), tables resident"}
-    if sharded and a.single:
-        # the step's two parts: every rank's local solve of its block (max over ranks), and the
-        # rest -- the one all-gather of the packed blocks + the finalize
-        local_only[0] = True
-        el_loc, _ = timed(1, a.steps, a.warmup)
-        local_only[0] = False
-        single["local_solve_ms"] = el_loc / a.steps * 1e3
-        single["allgather_finalize_ms"] = max(single["ms_per_step"] - single["local_solve_ms"], 0.0)
-        single["split_note"] = ("local_solve_ms: the same one-batch leg without the exchange (barrier + synchronize "
-                                "around K steps, max over ranks); allgather_finalize_ms: ms_per_step minus it")
-
-    # roofline of the dominant kernel.  COMPACT / SORTED / SWEEP: the single-solve leg's event
-    # bracket / K.  Otherwise (several kernels per step): one batch at a time with HIP events
-    # around each launch of the dominant kernel.
-    if one_kernel and brk:
-        el_r, kt1 = el1, {dom: (brk[0], a.steps)}
-        timing_note = ("two HIP events on the kernel's stream bracketing the single-solve leg's K back-to-back "
-                       "launches (no events between launches); avg = bracket / K")
-    else:
-        el_r, kt1 = timed(1, a.steps, a.warmup, (dom,))
-        timing_note = "HIP events around each launch on the kernel's stream, a separate one-batch leg"
-    for p in plans:
-        p.enable_timing(False)
-    dom_ms, dom_n = kt1[dom]
-    dom_avg_s = dom_ms / max(dom_n, 1) / 1e3
-    # FP64 basis (SURVEY §8d convention): per node 14 FLOP + 1 pow (counted as 1) for Student,
-    # over the nodes the solve evaluates -- counted on the device in one extra, untimed solve
-    # (SORTED evaluates each node of its bisection path once: cfg 4 ~17% of the reachable set,
-    # so the reachable-node basis would overstate the work), the reachable-node figure beside it
-    flop_node = {"student": 15.0, "gaussian": 14.0, "plackett": 16.0}[c.copula] + (9.0 if c.dim == 3 else 0.0)
-    nodes_eval = None
-    if a.strategy in ("compact", "sorted", "sweep") and not sharded:
-        plan.count_nodes(True)
-        step_fn(0)
-        torch.cuda.synchronize()
-        nodes_eval = plan.nodes_evaluated()
-        plan.count_nodes(False)
-        v2 = vars_[0].cpu().numpy()
-        assert np.array_equal(v2, vals, equal_nan=True), "node-count solve changed the VaR"
-    flop_launch = flop_node * (nodes_eval if nodes_eval is not None else plan.reach_nodes * per)
-    flop_reach = flop_node * plan.reach_nodes * per
-    fp64_tflops = flop_launch / dom_avg_s / 1e12 if dom_avg_s > 0 else 0.0
-    alg_bytes = 8.0 * plan.reach_nodes * per          # one f64 joint-mass word per reachable node
-    achieved_gbs = alg_bytes / dom_avg_s / 1e9 if dom_avg_s > 0 else 0.0
-    # PMC HBM bytes per launch (profiles/pmc_traffic_cfg<N>.json, tools/pmc_summary.py): attached only
-    # when that pass measured THIS library build (sha of libcvq.so), the same strategy and launch size
-    traffic, traffic_src = None, "no PMC pass of this library build (tools/pmc.sh)"
-    lib_sha = _lib_sha16()
-    pmc_path = os.path.join(REPO, "profiles", f"pmc_traffic_cfg{a.config}.json")
-    if os.path.exists(pmc_path):
-        try:
-            pm = json.load(open(pmc_path))
-            if (pm.get("lib_sha16") == lib_sha and pm.get("dates_per_launch") == per
-                    and pm.get("strategy") == a.strategy):
-                traffic = pm.get("hbm_bytes_per_launch")
-                traffic_src = f"profiles/pmc_traffic_cfg{a.config}.json (FETCH_SIZE + WRITE_SIZE, lib {lib_sha})"
-        except Exception:
-            traffic = None
-    pmc_gbs = traffic / dom_avg_s / 1e9 if (traffic is not None and dom_avg_s > 0) else None
-    # the binding roofline: FP64 VALU unless the measured HBM traffic is the larger fraction of its
-    # peak (the algorithmic bytes of SURVEY §8d are notional -- the solve never materialises the mass)
-    fp64_frac = fp64_tflops / FP64_PEAK_TFLOPS
-    hbm_bound = pmc_gbs is not None and pmc_gbs / HBM_PEAK_GBS > fp64_frac
     kernels = {k: {"avg_us": (v[0] / max(v[1], 1)) * 1e3, "launches": v[1]} for k, v in kt.items() if v[1]}
-    kernels_single = {k: {"avg_us": (v[0] / max(v[1], 1)) * 1e3, "launches": v[1]} for k, v in kt1.items() if v[1]}
+    if a.dump_outputs and rank == 0:
+        k_last = (a.steps - 1) % nf                   # the batch the last timed step ran on
+        dump_outputs(a.dump_outputs, (vars_[k_last] if not sharded else shardeds[k_last].var).cpu().numpy(),
+                     plans[k_last].solve_status())
 
-    e2e = None
-    if a.e2e and world == 1 and not strong:
-        e2e = end_to_end(a, c, block, per, plans, streams, vars_, args, vals, dev)
+    single = roofline = kernels_single = e2e = cpu = others = None
+    if a.full:
+        # one batch at a time; its back-to-back launches bracketed by two HIP events on the stream
+        # (the step is the one fused solve kernel for COMPACT / SORTED / SWEEP: the bracket over
+        # K steps / K is the kernel's average duration, as rocprofv3's kernel trace gives it)
+        one_kernel = a.strategy in ("compact", "sorted", "sweep") and not sharded
+        brk = []
+        if nf > 1 and a.single:
+            el1, _ = timed(1, a.steps, a.warmup, None, brk)
+            v1 = (vars_[0] if not sharded else shardeds[0].var).cpu().numpy()
+            assert np.array_equal(v1, vals, equal_nan=True), "single-solve leg changed the VaR"
+        else:
+            el1 = elapsed
+            brk = brk0
+        single = {"value": T_total * a.steps / el1, "unit": "VaR-dates/s", "ms_per_step": el1 / a.steps * 1e3,
+                  "inflight": 1, "steps": a.steps,
+                  "scope": "one calc_var-equivalent solve per step (utils/calc_var_class.py:109-175), tables resident"}
+        if sharded and a.single:
+            # the step's two parts: every rank's local solve of its block (max over ranks), and the
+            # rest -- the one all-gather of the packed blocks + the finalize
+            local_only[0] = True
+            el_loc, _ = timed(1, a.steps, a.warmup)
+            local_only[0] = False
+            single["local_solve_ms"] = el_loc / a.steps * 1e3
+            single["allgather_finalize_ms"] = max(single["ms_per_step"] - single["local_solve_ms"], 0.0)
+            single["split_note"] = ("local_solve_ms: the same one-batch leg without the exchange (barrier + "
+                                    "synchronize around K steps, max over ranks); allgather_finalize_ms: "
+                                    "ms_per_step minus it")
 
-    cpu = None
-    if rank == 0 and world == 1 and a.cpu_baseline:
-        cpu = cpu_baseline(c, ipt, uvs, ggp, ptf_mean, vals, a)
-
-    others = None
-    if rank == 0 and world == 1 and not strong:
-        others = other_configs(a)
-
-    if rank == 0:
+        # roofline of the dominant kernel.  COMPACT / SORTED / SWEEP: the single-solve leg's event
+        # bracket / K.  Otherwise (several kernels per step): one batch at a time with HIP events
+        # around each launch of the dominant kernel.
+        if one_kernel and brk:
+            el_r, kt1 = el1, {dom: (brk[0], a.steps)}
+            timing_note = ("two HIP events on the kernel's stream bracketing the single-solve leg's K back-to-back "
+                           "launches (no events between launches); avg = bracket / K")
+        else:
+            el_r, kt1 = timed(1, a.steps, a.warmup, (dom,))
+            timing_note = "HIP events around each launch on the kernel's stream, a separate one-batch leg"
+        for p in plans:
+            p.enable_timing(False)
+        dom_ms, dom_n = kt1[dom]
+        dom_avg_s = dom_ms / max(dom_n, 1) / 1e3
+        # FP64 basis (SURVEY §8d convention): per node 14 FLOP + 1 pow (counted as 1) for Student,
+        # over the nodes the solve evaluates -- counted on the device in one extra, untimed solve
+        # (SORTED evaluates each node of its bisection path once: cfg 4 ~17% of the reachable set,
+        # so the reachable-node basis would overstate the work), the reachable-node figure beside it
+        flop_node = {"student": 15.0, "gaussian": 14.0, "plackett": 16.0}[c.copula] + (9.0 if c.dim == 3 else 0.0)
+        nodes_eval = None
+        if a.strategy in ("compact", "sorted", "sweep") and not sharded:
+            plan.count_nodes(True)
+            step_fn(0)
+            torch.cuda.synchronize()
+            nodes_eval = plan.nodes_evaluated()
+            plan.count_nodes(False)
+            v2 = vars_[0].cpu().numpy()
+            assert np.array_equal(v2, vals, equal_nan=True), "node-count solve changed the VaR"
+        flop_launch = flop_node * (nodes_eval if nodes_eval is not None else plan.reach_nodes * per)
+        flop_reach = flop_node * plan.reach_nodes * per
+        fp64_tflops = flop_launch / dom_avg_s / 1e12 if dom_avg_s > 0 else 0.0
+        alg_bytes = 8.0 * plan.reach_nodes * per      # one f64 joint-mass word per reachable node
+        achieved_gbs = alg_bytes / dom_avg_s / 1e9 if dom_avg_s > 0 else 0.0
+        # PMC HBM bytes per launch (profiles/pmc_traffic_cfg<N>.json, tools/pmc_summary.py): attached only
+        # when that pass measured THIS library build (sha of libcvq.so), the same strategy and launch size
+        traffic, traffic_src = None, "no PMC pass of this library build (tools/pmc.sh)"
+        lib_sha = _lib_sha16()
+        pmc_path = os.path.join(REPO, "profiles", f"pmc_traffic_cfg{a.config}.json")
+        if os.path.exists(pmc_path):
+            try:
+                pm = json.load(open(pmc_path))
+                if (pm.get("lib_sha16") == lib_sha and pm.get("dates_per_launch") == per
+                        and pm.get("strategy") == a.strategy):
+                    traffic = pm.get("hbm_bytes_per_launch")
+                    traffic_src = (f"profiles/pmc_traffic_cfg{a.config}.json "
+                                   f"(FETCH_SIZE + WRITE_SIZE, lib {lib_sha})")
+            except Exception:
+                traffic = None
+        pmc_gbs = traffic / dom_avg_s / 1e9 if (traffic is not None and dom_avg_s > 0) else None
+        # the binding roofline: FP64 VALU unless the measured HBM traffic is the larger fraction of its
+        # peak (the algorithmic bytes of SURVEY §8d are notional -- the solve never materialises the mass)
+        fp64_frac = fp64_tflops / FP64_PEAK_TFLOPS
+        hbm_bound = pmc_gbs is not None and pmc_gbs / HBM_PEAK_GBS > fp64_frac
+        kernels_single = {k: {"avg_us": (v[0] / max(v[1], 1)) * 1e3, "launches": v[1]}
+                          for k, v in kt1.items() if v[1]}
         kname = {"prefix": "k_mass (joint-mass row prefix)",
                  "direct": "k_direct (per-date slab-on-the-fly solve)",
                  "compact": "k_compact (per-date solve, block tail)",
                  "sorted": "k_sorted (per-date solve over the v*-sorted node list)",
                  "sweep": "k_sorted<SWEEP> (per-date solve, one pass per bisection cell)"}[a.strategy]
+        roofline = {"bound": "hbm" if hbm_bound else "fp64-valu",
+                    "achieved": pmc_gbs if hbm_bound else fp64_tflops,
+                    "peak": HBM_PEAK_GBS if hbm_bound else FP64_PEAK_TFLOPS,
+                    "unit": "GB/s" if hbm_bound else "TFLOP/s",
+                    "frac": pmc_gbs / HBM_PEAK_GBS if hbm_bound else fp64_frac,
+                    "traffic": traffic, "traffic_source": traffic_src, "lib_sha16": lib_sha, "kernel": kname,
+                    "flop_per_node": flop_node,
+                    "flop_basis": "nodes evaluated (device count)" if nodes_eval is not None
+                                  else "reachable nodes",
+                    "nodes_evaluated_per_date": (nodes_eval / per) if nodes_eval is not None else None,
+                    "reach_nodes_per_date": plan.reach_nodes,
+                    "dates_per_launch": per, "flop_per_launch": flop_launch,
+                    "avg_launch_us": dom_avg_s * 1e6, "launches": dom_n,
+                    "timing": timing_note,
+                    "event_leg_ms_per_step": el_r / a.steps * 1e3,
+                    "reach_basis": {"flop_per_launch": flop_reach,
+                                    "frac": flop_reach / dom_avg_s / 1e12 / FP64_PEAK_TFLOPS
+                                    if dom_avg_s > 0 else 0.0},
+                    "fp64": {"achieved": fp64_tflops, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
+                             "frac": fp64_frac},
+                    "hbm": {"pmc_bytes_per_launch": traffic, "pmc_achieved": pmc_gbs,
+                            "pmc_frac": pmc_gbs / HBM_PEAK_GBS if pmc_gbs is not None else None,
+                            "alg_bytes_per_launch": alg_bytes, "alg_achieved": achieved_gbs,
+                            "alg_frac": achieved_gbs / HBM_PEAK_GBS, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                            "note": "alg_*: 8 B x reachable nodes (SURVEY §8d), notional -- the solve never "
+                                    "writes the joint mass; pmc_*: measured FETCH_SIZE + WRITE_SIZE"}}
+
+        if a.e2e and world == 1 and not strong:
+            e2e = end_to_end(a, c, block, per, plans, streams, vars_, args, vals, dev)
+
+        if rank == 0 and world == 1 and a.cpu_baseline:
+            cpu = cpu_baseline(c, ipt, uvs, ggp, ptf_mean, vals, a)
+
+        if rank == 0 and world == 1 and not strong:
+            others = other_configs(a)
+
+    if rank == 0:
         out = {
             "metric": METRICS.get(a.config, f"VaR dates solved/sec, {c.name}"),
             "value": value,
@@ -396,32 +441,8 @@ def main():
                        "strategy": a.strategy, "inflight": nf},
             "single_solve": single,
             "host_enqueue_ms_per_step": enq_ms[0] if enq_ms else None,
-            "roofline": {"bound": "hbm" if hbm_bound else "fp64-valu",
-                         "achieved": pmc_gbs if hbm_bound else fp64_tflops,
-                         "peak": HBM_PEAK_GBS if hbm_bound else FP64_PEAK_TFLOPS,
-                         "unit": "GB/s" if hbm_bound else "TFLOP/s",
-                         "frac": pmc_gbs / HBM_PEAK_GBS if hbm_bound else fp64_frac,
-                         "traffic": traffic, "traffic_source": traffic_src, "lib_sha16": lib_sha, "kernel": kname,
-                         "flop_per_node": flop_node,
-                         "flop_basis": "nodes evaluated (device count)" if nodes_eval is not None
-                                       else "reachable nodes",
-                         "nodes_evaluated_per_date": (nodes_eval / per) if nodes_eval is not None else None,
-                         "reach_nodes_per_date": plan.reach_nodes,
-                         "dates_per_launch": per, "flop_per_launch": flop_launch,
-                         "avg_launch_us": dom_avg_s * 1e6, "launches": dom_n,
-                         "timing": timing_note,
-                         "event_leg_ms_per_step": el_r / a.steps * 1e3,
-                         "reach_basis": {"flop_per_launch": flop_reach,
-                                         "frac": flop_reach / dom_avg_s / 1e12 / FP64_PEAK_TFLOPS
-                                         if dom_avg_s > 0 else 0.0},
-                         "fp64": {"achieved": fp64_tflops, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
-                                  "frac": fp64_frac},
-                         "hbm": {"pmc_bytes_per_launch": traffic, "pmc_achieved": pmc_gbs,
-                                 "pmc_frac": pmc_gbs / HBM_PEAK_GBS if pmc_gbs is not None else None,
-                                 "alg_bytes_per_launch": alg_bytes, "alg_achieved": achieved_gbs,
-                                 "alg_frac": achieved_gbs / HBM_PEAK_GBS, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                 "note": "alg_*: 8 B x reachable nodes (SURVEY §8d), notional -- the solve never "
-                                         "writes the joint mass; pmc_*: measured FETCH_SIZE + WRITE_SIZE"}},
+            "full": bool(a.full),
+            "roofline": roofline,
             "kernels": kernels,
             "kernels_single": kernels_single,
             "forecast_stage_s": t_fc,
@@ -438,6 +459,14 @@ def main():
         dist.destroy_process_group()
 
 
+def dump_outputs(out_dir, var, iterations):
+    """--dump-outputs: what the last timed step returned, one float64 .npy per array (the inputs
+    are seeded, so two builds run with the same arguments can be compared array for array)."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "var.npy"), np.ascontiguousarray(var, dtype=np.float64))
+    np.save(os.path.join(out_dir, "iterations.npy"), np.array([iterations], dtype=np.float64))
+
+
 def other_configs(a):
     """The other BASELINE configs at full size (auto strategy): batches in flight, the single solve
     (one batch at a time) and end to end -- each a fresh child `bench.py` process started after this
@@ -452,7 +481,7 @@ def other_configs(a):
     cfgs = [5, 3, 4] if spec == "auto" else [int(v) for v in spec.split(",") if v.strip()]
     res = {}
     for cn in cfgs:
-        cmd = [sys.executable, os.path.abspath(__file__), "--config", str(cn), "--steps", "20",
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--config", str(cn), "--steps", "20",
                "--warmup", "3", "--e2e", "1", "--cpu-baseline", "0", "--other-configs", "none"]
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)

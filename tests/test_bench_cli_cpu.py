@@ -100,3 +100,21 @@ def test_other_configs_selection_and_record(monkeypatch):
     assert all("--other-configs" in c and c[c.index("--other-configs") + 1] == "none" for c in calls)
     assert res["cfg5"]["in_flight"] == 1.0e8
     assert all("--inflight" not in c for c in calls)                  # the default batches in flight
+    assert all("--full" in c for c in calls)                          # the children's extra legs are recorded
+
+
+def test_full_is_off_by_default_and_dump_writes_float64(tmp_path):
+    """A plain run measures the headline leg only (--full off); --dump-outputs writes the last
+    step's VaR vector and iteration count as float64 .npy files, NaN kept."""
+    import numpy as np
+    a = _args("--gpus", "1", "--steps", "7", "--warmup", "2")
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = _args("--full", "--dump-outputs", str(tmp_path / "o"))
+    assert a.full is True and a.dump_outputs == str(tmp_path / "o")
+    var = np.array([-0.25, np.nan, -1.5])
+    bench.dump_outputs(a.dump_outputs, var, 23)
+    assert sorted(os.listdir(a.dump_outputs)) == ["iterations.npy", "var.npy"]
+    got = np.load(os.path.join(a.dump_outputs, "var.npy"))
+    assert got.dtype == np.float64 and np.array_equal(got, var, equal_nan=True)
+    it = np.load(os.path.join(a.dump_outputs, "iterations.npy"))
+    assert it.dtype == np.float64 and it.tolist() == [23.0]

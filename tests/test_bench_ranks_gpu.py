@@ -46,10 +46,19 @@ def _bench(args, nproc, self_launch=False):
 COMMON = ["--steps", "3", "--warmup", "1", "--cpu-baseline", "0", "--e2e", "0", "--single", "0", "--inflight", "2"]
 
 
-def test_two_ranks_weak_and_strong_match_one_rank():
-    one = _bench(COMMON + ["--dates-per-gpu", "240"], 1)
+def test_two_ranks_weak_and_strong_match_one_rank(tmp_path):
+    import numpy as np
+    one = _bench(COMMON + ["--dates-per-gpu", "240", "--dump-outputs", str(tmp_path)], 1)
+    # a plain run: the headline leg only, and the last step's outputs written as float64
+    assert one["full"] is False and one["single_solve"] is None and one["roofline"] is None
+    assert one["steps"] == 3 and one["ms_per_step"] > 0
+    var = np.load(tmp_path / "var.npy")
+    assert var.dtype == np.float64 and var.shape == (240,)
+    assert float(np.nansum(var)) == one["var_checksum"]
+    assert np.load(tmp_path / "iterations.npy").shape == (1,)
     weak = _bench(COMMON + ["--dates-per-gpu", "120"], 2)           # 2 x 120 dates of the same series
-    strong = _bench(COMMON + ["--global-dates", "240", "--single", "1"], 2)   # 240 dates split 120 / 120
+    # 240 dates split 120 / 120; --full: the single-solve leg and its local / exchange split
+    strong = _bench(COMMON + ["--global-dates", "240", "--single", "1", "--full"], 2)
     assert one["var_nan"] == 0
     for r in (weak, strong):
         assert r["n_gpus"] == 2 and r["config"]["global_dates"] == 240

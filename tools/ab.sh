@@ -9,7 +9,7 @@ mkdir -p $out
 for rep in 1 2; do
   for v in "$@"; do
     echo -n "$v rep $rep: "
-    CVQ_LIB=$GRAFT_REPO_ROOT/build_variants/$v/libcvq.so timeout -k 10 120 python bench.py --cpu-baseline 0 $args \
+    CVQ_LIB=$PWD/build_variants/$v/libcvq.so timeout -k 10 120 python bench.py --full --cpu-baseline 0 $args \
         > $out/${v}_$rep.json 2> $out/${v}_$rep.err
     rc=$?
     if [ -s $out/${v}_$rep.json ]; then

@@ -10,7 +10,7 @@ for rep in 1 2 3; do
   i=0
   for v in "$@"; do
     i=$((i+1))
-    env $v timeout -k 10 120 python bench.py --cpu-baseline 0 $args > $out/v${i}_$rep.json 2> $out/v${i}_$rep.err
+    env $v timeout -k 10 120 python bench.py --full --cpu-baseline 0 $args > $out/v${i}_$rep.json 2> $out/v${i}_$rep.err
     rc=$?
     if [ -s $out/v${i}_$rep.json ]; then
       echo -n "$v rep $rep: "; python3 tools/bench_brief.py < $out/v${i}_$rep.json

@@ -16,7 +16,7 @@ echo "smoke ok"
 bash tools/pmc.sh $tag > $out/pmc.txt 2>&1 || { echo "pmc failed"; tail -20 $out/pmc.txt; exit 1; }
 cp gpurun_out/pmc_traffic_cfg2.json profiles/pmc_traffic_cfg2.json
 tail -2 $out/pmc.txt
-timeout -k 10 600 python3 bench.py > $out/bench_default.json 2> $out/bench_default.err \
+timeout -k 10 600 python3 bench.py --full > $out/bench_default.json 2> $out/bench_default.err \
     || { echo "bench failed rc=$?"; tail -20 $out/bench_default.err; exit 1; }
 python3 tools/bench_brief.py < $out/bench_default.json
 bash tools/profile_default.sh $tag > $out/profile.txt 2>&1 || { echo "profile failed"; tail -20 $out/profile.txt; exit 1; }

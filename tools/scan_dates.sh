@@ -9,7 +9,7 @@ mkdir -p $out
 scan() {   # config, dates...
   local c=$1; shift
   for d in "$@"; do
-    timeout -k 10 240 python3 bench.py --config $c --dates-per-gpu $d --inflight 1 --steps 20 --warmup 3 \
+    timeout -k 10 240 python3 bench.py --full --config $c --dates-per-gpu $d --inflight 1 --steps 20 --warmup 3 \
         --e2e 0 --cpu-baseline 0 "${EXTRA[@]}" > $out/c${c}_d${d}.json 2> $out/c${c}_d${d}.err \
       || { echo "cfg $c dates $d failed rc=$?"; tail -5 $out/c${c}_d${d}.err; exit 1; }
     echo "cfg $c dates $d: $(python3 tools/bench_brief.py < $out/c${c}_d${d}.json)" | tee -a $out/dates_scan.txt

@@ -13,7 +13,7 @@ tail -2 $out/pytest.txt
 for c in "${@:-3 5}"; do
   for d in 0 625; do
     extra=(); [ $d != 0 ] && extra=(--dates-per-gpu $d --inflight 1)
-    timeout -k 10 240 python3 bench.py --config $c --steps 20 --warmup 3 --e2e 0 --cpu-baseline 0 "${extra[@]}" \
+    timeout -k 10 240 python3 bench.py --full --config $c --steps 20 --warmup 3 --e2e 0 --cpu-baseline 0 "${extra[@]}" \
         > $out/c${c}_d$d.json 2> $out/c${c}_d$d.err || { echo "bench $c failed"; tail -5 $out/c${c}_d$d.err; exit 1; }
     echo "cfg $c dates $d: $(python3 tools/bench_brief.py < $out/c${c}_d$d.json)" | tee -a $out/bench.txt
   done

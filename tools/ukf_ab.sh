@@ -11,7 +11,7 @@ CVQ_LIB=$GRAFT_REPO_ROOT/build_variants/ukf2/libcvq.so timeout -k 10 300 python3
     > $out/pytest.txt 2>&1 || { echo "pytest failed"; tail -30 $out/pytest.txt; exit 1; }
 tail -1 $out/pytest.txt
 for r in 1 2; do for v in base ukf2; do
-  CVQ_LIB=$GRAFT_REPO_ROOT/build_variants/$v/libcvq.so timeout -k 10 240 python3 bench.py --config 5 --steps 20 \
+  CVQ_LIB=$PWD/build_variants/$v/libcvq.so timeout -k 10 240 python3 bench.py --full --config 5 --steps 20 \
       --warmup 3 --cpu-baseline 0 --other-configs none > $out/c5_${v}_$r.json 2> $out/c5_${v}_$r.err \
     || { echo "bench $v failed"; tail -5 $out/c5_${v}_$r.err; exit 1; }
   echo "cfg 5 $v rep $r: $(python3 tools/bench_brief.py < $out/c5_${v}_$r.json)" | tee -a $out/ab.txt
