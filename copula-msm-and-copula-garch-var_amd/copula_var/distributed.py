@@ -55,11 +55,14 @@ class ShardedVaR:
     local(hdr, snaps): solve this rank's block into those two views.
     finalize(blocks, var): full VaR vector from the gathered blocks [world, block_len].
     check(): optional convergence check after the finalize (raises on failure).
+    es_local(var_block, es_block): optional; Expected Shortfall of this rank's dates from
+    their solved VaR (both views of length hi - lo), for expected_shortfall().
     """
 
     def __init__(self, T_total: int, stride: int, local: Callable, finalize: Callable,
                  device: torch.device, group=None, check: Optional[Callable] = None,
-                 block_len: Optional[int] = None, hdr_off: Optional[int] = None):
+                 block_len: Optional[int] = None, hdr_off: Optional[int] = None,
+                 es_local: Optional[Callable] = None):
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
@@ -67,6 +70,7 @@ class ShardedVaR:
         self.lo, self.hi, self.per = shard(self.T_total, self.rank, self.world)
         self.stride = int(stride)
         self._local, self._finalize, self._check = local, finalize, check
+        self._es_local = es_local
         if hdr_off is None:                                   # snapshots, padded to 16 B, then the header
             hdr_off = (self.per * self.stride + 1) & ~1
         self.hdr_off = int(hdr_off)
@@ -94,6 +98,17 @@ class ShardedVaR:
             self._check()
         return self.var
 
+    def expected_shortfall(self) -> torch.Tensor:
+        """Full Expected Shortfall vector on every rank, after solve(): each rank fills its own
+        dates from var[lo:hi] into a NaN-padded [per] block; one all-gather."""
+        if self._es_local is None:
+            raise RuntimeError("this ShardedVaR was built without es_local")
+        blk = torch.full((self.per,), float("nan"), dtype=torch.float64, device=self.var.device)
+        if self.hi > self.lo:
+            self._es_local(self.var[self.lo:self.hi], blk[: self.hi - self.lo])
+        out = blk if not dist.is_initialized() else _gather(blk, self.world, self.group)
+        return out[: self.T_total]
+
 
 def device_sharded_var(plan, args, T_total: int, device: torch.device, group=None) -> ShardedVaR:
     """ShardedVaR wired to a QuadraturePlan's device entry points (plan holds this rank's block).
@@ -112,5 +127,9 @@ def device_sharded_var(plan, args, T_total: int, device: torch.device, group=Non
     def finalize(blocks, var):
         plan.solve_finalize_packed(args, blocks.data_ptr(), world, per, T_total, var.data_ptr())
 
+    def es_local(var_block, es_block):
+        plan.set_stream(torch.cuda.current_stream(device).cuda_stream)
+        plan.expected_shortfall_device(args, var_block.data_ptr(), es_block.data_ptr())
+
     return ShardedVaR(T_total, stride, local, finalize, device, group, check=plan.solve_status,
-                      block_len=block_len, hdr_off=hdr_off)
+                      block_len=block_len, hdr_off=hdr_off, es_local=es_local)

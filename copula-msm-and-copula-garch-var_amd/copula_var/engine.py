@@ -190,13 +190,13 @@ class QuadraturePlan:
         if self._wide is not None:
             self._wide.set_stream(stream_handle)
 
-    KERNELS = {"tables": 0, "mass": 1, "solve": 2, "finalize": 3, "slab": 4}
+    KERNELS = {"tables": 0, "mass": 1, "solve": 2, "finalize": 3, "slab": 4, "moments": 5}
 
     def enable_timing(self, on=True) -> None:
         """Record HIP events around kernel launches on the plan's stream: True = every
         kind, False = off, or an iterable of kind names (e.g. ("solve",))."""
         if on is True or on is False:
-            mask = 0x1F if on else 0
+            mask = 0x3F if on else 0
         else:
             mask = 0
             for k in on:
@@ -299,6 +299,44 @@ class QuadraturePlan:
         it = C.c_int32(0)
         N.check(N.lib().cvq_solve(self._h, C.byref(args), N.ptr(out), C.byref(it), N.MEM_HOST), "cvq_solve")
         return out, int(it.value)
+
+    # ------------------------------------------------------------ tail moments / Expected Shortfall
+    # (no reference counterpart; they run on this plan whatever its strategy: the moment
+    # kernel takes any bounds, so nothing is routed to the sibling)
+    def tail_moments(self, bounds) -> Tuple[np.ndarray, np.ndarray]:
+        """(m0, m1) per date of the slab (bounds[t, 0], bounds[t, 1]]: m0 = sum of the member
+        nodes' mass (compute_integral's value to rounding), m1 = sum of level x mass."""
+        b = N.f64(bounds)
+        if b.shape != (self.T, 2):
+            raise ValueError(f"bounds must have shape ({self.T}, 2)")
+        m0, m1 = np.empty(self.T), np.empty(self.T)
+        N.check(N.lib().cvq_slab_moments(self._h, N.ptr(b), N.ptr(m0), N.ptr(m1), N.MEM_HOST), "cvq_slab_moments")
+        return m0, m1
+
+    def tail_moments_device(self, bounds_ptr: int, m0_ptr: int, m1_ptr: int) -> None:
+        """tail_moments on device buffers, in stream order (no host synchronisation)."""
+        N.check(N.lib().cvq_slab_moments(self._h, C.c_void_p(bounds_ptr), C.c_void_p(m0_ptr), C.c_void_p(m1_ptr),
+                                         N.MEM_DEVICE), "cvq_slab_moments")
+
+    def expected_shortfall(self, var, ptf_mean: float = 0.0, lower: float = -100.0) -> Tuple[np.ndarray, np.ndarray]:
+        """(es, m0) per date for a solved VaR vector (as calc_var returns it, ptf_mean included):
+        es = m1 / m0 + ptf_mean over (lower, var - ptf_mean], the mean portfolio return at or
+        below the VaR; m0 is the mass found there.  NaN where var is NaN or m0 == 0."""
+        v = N.f64(var)
+        if v.shape != (self.T,):
+            raise ValueError(f"var must have shape ({self.T},)")
+        args = solve_args(ptf_mean, lower=lower)
+        es, m0 = np.empty(self.T), np.empty(self.T)
+        N.check(N.lib().cvq_expected_shortfall(self._h, C.byref(args), N.ptr(v), N.ptr(es), N.ptr(m0), N.MEM_HOST),
+                "cvq_expected_shortfall")
+        return es, m0
+
+    def expected_shortfall_device(self, args: N.CvqSolveArgs, var_ptr: int, es_ptr: int,
+                                  m0_ptr: Optional[int] = None) -> None:
+        """expected_shortfall on device buffers (args: lower and ptf_mean are read), in stream
+        order behind e.g. solve_device(check=False): no host synchronisation."""
+        N.check(N.lib().cvq_expected_shortfall(self._h, C.byref(args), C.c_void_p(var_ptr), C.c_void_p(es_ptr),
+                                               C.c_void_p(m0_ptr or 0), N.MEM_DEVICE), "cvq_expected_shortfall")
 
     # ------------------------------------------------------------ device-resident solve
     def solve_device(self, args: N.CvqSolveArgs, var_ptr: int, check: bool = False) -> Optional[int]:

@@ -43,7 +43,7 @@ def plot_var_and_returns(series: dict, portfolio_returns, path: str) -> None:
     plt.close()
 
 
-def main(argv=None) -> int:
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--prices", required=True, help="CSV of adjusted closes (date index, one column per ticker)")
     ap.add_argument("--returns", action="store_true", help="the CSV already holds log returns x 100")
@@ -59,12 +59,18 @@ def main(argv=None) -> int:
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--out", default=None, help="CSV of the VaR series")
     ap.add_argument("--plot", default=None, help="PNG of main.py's VaR / returns plot")
-    a = ap.parse_args(argv)
+    ap.add_argument("--es", action="store_true",
+                    help="also compute the Expected Shortfall below each VaR (an <estimation>_es column in --out)")
+    return ap
+
+
+def main(argv=None) -> int:
+    a = build_parser().parse_args(argv)
 
     df = load_returns_csv(a.prices, prices=not a.returns)[a.tickers]
     SharedCacheIndexReturns.returns_cache[(tuple(a.tickers), a.start, a.end)] = df
     weights = np.array(a.weights if a.weights else [1.0 / len(a.tickers)] * len(a.tickers))
-    out, runs = {}, {}
+    out, runs, es = {}, {}, {}
     for est in a.estimation:
         calc = ValueAtRiskCalculationFactory.create_var_calculator(copula_type=a.copula, estimation_type=est)
         kw = {"k": a.k} if est == "msm" else {}
@@ -72,11 +78,19 @@ def main(argv=None) -> int:
                                            weights=weights, device=a.device, **kw)
         out[est] = runs[est].calc_var()
         print(f"{est}/{a.copula}: {out[est].size} dates, mean VaR {np.nanmean(out[est]):.4f}", file=sys.stderr)
+        if a.es:
+            es[est] = runs[est].calc_es(var=out[est])
+            print(f"{est}/{a.copula}: mean ES {np.nanmean(es[est]):.4f}", file=sys.stderr)
     first = runs[a.estimation[0]]
     portfolio = first.out_sample_data.mean(axis=1).to_numpy()                    # main.py:73
     if a.out:
         idx = first.out_sample_data.index[:len(out[a.estimation[0]])]
-        frame = pd.DataFrame({f"var_{k}": v for k, v in out.items()}, index=idx)
+        cols = {}
+        for k, v in out.items():
+            cols[f"var_{k}"] = v
+            if k in es:
+                cols[f"{k}_es"] = es[k]                     # next to its VaR column
+        frame = pd.DataFrame(cols, index=idx)
         frame["portfolio_return"] = portfolio[:len(frame)]
         frame.to_csv(a.out)
     if a.plot:

@@ -123,6 +123,16 @@ class ValueAtRiskCalcualtion:
         print(f"calc_var function execution time: {time.time() - start_time:.4f} seconds")
         return var
 
+    def calc_es(self, obj_var=0.05, first_guess=-3, second_guess=(-3.5, -2), var=None):
+        """Per-date Expected Shortfall (T,): the mean portfolio return given that it falls at or
+        below the VaR, on the VaR's own nested grid (no reference counterpart).  var=None solves
+        the VaR first (calc_var with these arguments).  The mass found below each VaR is kept
+        in last_tail_mass."""
+        if var is None:
+            var = self.calc_var(obj_var, first_guess, second_guess)
+        es, self.last_tail_mass = self.plan.expected_shortfall(np.asarray(var, dtype=np.float64), self.ptf_mean)
+        return es
+
     def compute_integral(self, bounds):
         """I_t(a, b] for every date t (calc_var_class.py:179-212), one device launch."""
         return self.plan.compute_integral(np.asarray(bounds, dtype=np.float64))

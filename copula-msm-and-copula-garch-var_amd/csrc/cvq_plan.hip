@@ -146,6 +146,12 @@ struct cvq_plan {
     int* d_err = nullptr;
     long long capIO = 0;
     double* d_io = nullptr;      // bounds (2T) + out (T) / var (T)
+    // tail moments (cvq_slab_moments / cvq_expected_shortfall): their own per-date tables and
+    // per-chunk partial sums, so the solve's tables_valid / mass_valid state is never touched
+    long long capMom = 0;
+    double* d_mA = nullptr;      // [T][dim][n]
+    double* d_mB = nullptr;
+    double* d_mpart = nullptr;   // [T][chunks][2]
     unsigned long long* d_stamps = nullptr;   // diagnostic phase stamps (CVQ_STAMPS=1)
     bool count_nodes = false;    // cvq_plan_count_nodes: solves record their node counts (stamps)
     bool nodes_valid = false;    // the last solve recorded them
@@ -197,7 +203,7 @@ struct cvq_plan {
 };
 
 namespace {
-enum TimedKernel { TK_TABLES = 0, TK_MASS = 1, TK_SOLVE = 2, TK_FINALIZE = 3, TK_SLAB = 4, TK_COUNT = 5 };
+enum TimedKernel { TK_TABLES = 0, TK_MASS = 1, TK_SOLVE = 2, TK_FINALIZE = 3, TK_SLAB = 4, TK_MOMENTS = 5, TK_COUNT = 6 };
 
 struct TimedScope {
     cvq_plan* p;
@@ -844,6 +850,10 @@ int launch_sorted(const StaticDev& S, const SolveConst& P, const SortedGeom& G, 
                   const double* a, const double* tA, const double* tB, const double* pi, bool fused, int mode,
                   const double* bounds, double* out, double* snaps, Header* hdr, double* stamps,
                   bool sweep, size_t abi);                                            // cvq_sorted.hip
+int moments_chunk_count(int dim, int nrows);                                          // cvq_moments.hip
+int launch_moments(const StaticDev& S, long long T, hipStream_t stream, const double* a, const double* pi, double* tA,
+                   double* tB, double* part, const double* bounds, const double* var, double lower, double ptf_mean,
+                   double* out0, double* out1, size_t abi);
 }
 namespace {
 
@@ -1120,6 +1130,24 @@ int ensure_io(cvq_plan* p, long long need) {
     return CVQ_OK;
 }
 
+// Tail moments: scratch for the current batch, then tables -> partial sums -> per-date sums.
+int run_moments(cvq_plan* p, const double* bounds, const double* var, double lower, double ptf_mean, double* out0,
+                double* out1) {
+    CVQ_HIP_CHECK(hipSetDevice(p->device));
+    if (p->T > p->capMom) {
+        const size_t tab = (size_t)p->T * p->S.dim * p->S.n;
+        const size_t part = (size_t)p->T * moments_chunk_count(p->S.dim, p->S.nrows) * 2;
+        p->capMom = 0;
+        int rc;
+        if ((rc = dev_alloc(&p->d_mA, tab)) || (rc = dev_alloc(&p->d_mB, tab)) || (rc = dev_alloc(&p->d_mpart, part)))
+            return rc;
+        p->capMom = p->T;
+    }
+    TimedScope ts(p, TK_MOMENTS);
+    return launch_moments(p->S, p->T, p->stream, p->in_a, p->in_pi, p->d_mA, p->d_mB, p->d_mpart, bounds, var, lower,
+                          ptf_mean, out0, out1, kernel_abi_key());
+}
+
 // Invert a symmetric dim x dim matrix (2 or 3) by cofactors; returns det.
 double invert(const double* R, int d, double* Ri) {
     if (d == 2) {
@@ -1142,7 +1170,7 @@ double invert(const double* R, int d, double* Ri) {
 extern "C" {
 
 const char* cvq_last_error(void) { return g_err.c_str(); }
-int32_t cvq_version(void) { return 10000; }
+int32_t cvq_version(void) { return 10100; }
 
 int32_t cvq_device_count(int32_t* count) {
     CVQ_REQUIRE(count != nullptr, CVQ_ERR_INVALID, "count is NULL");
@@ -1383,6 +1411,7 @@ int32_t cvq_plan_destroy(cvq_plan* p) {
     for (void* b : {(void*)p->d_x, (void*)p->d_F, (void*)p->d_phi, (void*)p->d_uvs, (void*)p->d_cf, (void*)p->d_kmax,
                     (void*)p->d_off, (void*)p->d_a, (void*)p->d_pi, (void*)p->d_tA, (void*)p->d_tB,
                     (void*)p->d_C, (void*)p->d_snap, (void*)p->d_hdr, (void*)p->d_err, (void*)p->d_io, (void*)p->d_stamps,
+                    (void*)p->d_mA, (void*)p->d_mB, (void*)p->d_mpart,
                     (void*)p->d_cutfix, (void*)p->d_kcut, (void*)p->d_fpair, (void*)p->d_ccount, (void*)p->d_tlist, (void*)p->d_tvs, (void*)p->d_defer, (void*)p->d_vstar, (void*)p->d_bucket, (void*)p->d_sidx, (void*)p->d_svs,
                     (void*)p->d_tree, (void*)p->d_pass,
                     (void*)p->d_pidx, (void*)p->d_pvs})
@@ -1558,6 +1587,44 @@ int32_t cvq_slab(cvq_plan* p, const double* bounds, double* out, int32_t mem) {
     CVQ_HIP_CHECK(hipMemcpyAsync(p->d_io, bounds, 2 * p->T * sizeof(double), hipMemcpyHostToDevice, p->stream));
     if ((rc = launch_slab(p, p->d_io, p->d_io + 2 * p->T))) return rc;
     CVQ_HIP_CHECK(hipMemcpyAsync(out, p->d_io + 2 * p->T, p->T * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    CVQ_HIP_CHECK(hipStreamSynchronize(p->stream));
+    return CVQ_OK;
+}
+
+int32_t cvq_slab_moments(cvq_plan* p, const double* bounds, double* m0_out, double* m1_out, int32_t mem) {
+    cvq::DeviceScope device_scope;                 // the caller's current device, restored on return
+    CVQ_REQUIRE(p != nullptr && bounds != nullptr && m0_out != nullptr && m1_out != nullptr, CVQ_ERR_INVALID,
+                "NULL argument");
+    CVQ_REQUIRE(p->T > 0, CVQ_ERR_STATE, "cvq_set_dates must be called first");
+    if (mem == CVQ_MEM_DEVICE) return run_moments(p, bounds, nullptr, 0.0, 0.0, m0_out, m1_out);
+    const long long T = p->T;
+    int rc = ensure_io(p, 4 * T);
+    if (rc) return rc;
+    CVQ_HIP_CHECK(hipSetDevice(p->device));
+    CVQ_HIP_CHECK(hipMemcpyAsync(p->d_io, bounds, 2 * T * sizeof(double), hipMemcpyHostToDevice, p->stream));
+    if ((rc = run_moments(p, p->d_io, nullptr, 0.0, 0.0, p->d_io + 2 * T, p->d_io + 3 * T))) return rc;
+    CVQ_HIP_CHECK(hipMemcpyAsync(m0_out, p->d_io + 2 * T, T * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    CVQ_HIP_CHECK(hipMemcpyAsync(m1_out, p->d_io + 3 * T, T * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    CVQ_HIP_CHECK(hipStreamSynchronize(p->stream));
+    return CVQ_OK;
+}
+
+int32_t cvq_expected_shortfall(cvq_plan* p, const cvq_solve_args* a, const double* var, double* es_out,
+                               double* m0_out, int32_t mem) {
+    cvq::DeviceScope device_scope;                 // the caller's current device, restored on return
+    CVQ_REQUIRE(p != nullptr && a != nullptr && var != nullptr && es_out != nullptr, CVQ_ERR_INVALID,
+                "NULL argument");
+    CVQ_REQUIRE(p->T > 0, CVQ_ERR_STATE, "cvq_set_dates must be called first");
+    if (mem == CVQ_MEM_DEVICE) return run_moments(p, nullptr, var, a->lower, a->ptf_mean, m0_out, es_out);
+    const long long T = p->T;
+    int rc = ensure_io(p, 3 * T);
+    if (rc) return rc;
+    CVQ_HIP_CHECK(hipSetDevice(p->device));
+    CVQ_HIP_CHECK(hipMemcpyAsync(p->d_io, var, T * sizeof(double), hipMemcpyHostToDevice, p->stream));
+    if ((rc = run_moments(p, nullptr, p->d_io, a->lower, a->ptf_mean, p->d_io + T, p->d_io + 2 * T))) return rc;
+    if (m0_out)
+        CVQ_HIP_CHECK(hipMemcpyAsync(m0_out, p->d_io + T, T * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    CVQ_HIP_CHECK(hipMemcpyAsync(es_out, p->d_io + 2 * T, T * sizeof(double), hipMemcpyDeviceToHost, p->stream));
     CVQ_HIP_CHECK(hipStreamSynchronize(p->stream));
     return CVQ_OK;
 }

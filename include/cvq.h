@@ -110,8 +110,9 @@ int32_t cvq_plan_info(const cvq_plan* plan, int64_t* reach_nodes, int32_t* rows)
 
 /* Per-kernel timing with HIP events recorded on the plan's stream (bench.py's
  * live roofline).  kind: 0 tables, 1 joint-mass/prefix, 2 solve, 3 finalize,
- * 4 slab.  cvq_plan_timing(mask) times the kinds whose bit (1 << kind) is set
- * (0 = off, 0x1F = all) and clears previous records. */
+ * 4 slab, 5 tail moments (cvq_slab_moments / cvq_expected_shortfall: their tables,
+ * partial sums and finish together).  cvq_plan_timing(mask) times the kinds whose
+ * bit (1 << kind) is set (0 = off, 0x3F = all) and clears previous records. */
 int32_t cvq_plan_timing(cvq_plan* plan, int32_t enable);
 int32_t cvq_plan_kernel_time(cvq_plan* plan, int32_t kind, double* total_ms, int32_t* launches);
 /* Diagnostic build aid: per-date phase timestamps (s_memtime) of the last DIRECT
@@ -154,6 +155,29 @@ int32_t cvq_set_fast_hint(cvq_plan* plan, int32_t on);
  * out[t] = integral of the joint copula density over the nested grid of
  * (bounds[t][0], bounds[t][1]] for date t.  bounds [T][2], out [T]. */
 int32_t cvq_slab(cvq_plan* plan, const double* bounds, double* out, int32_t mem);
+
+/* No reference counterpart.  Tail moments of the slab (bounds[t][0], bounds[t][1]] on the
+ * same nested grid, membership rule (create_grids.py:102-108, Q9/Q10) and node masses as
+ * cvq_slab:  m0_out[t] = sum of the member nodes' mass (cvq_slab's value to rounding),
+ * m1_out[t] = sum of level x mass, level = w[0] x[i_inner] + sum_c w[c + 1] x[i_c].
+ * Any bounds are valid (no v_cap limit, on every strategy); a NaN bound gives 0, 0.
+ * Each date is a fixed-order sum over its own row chunks: results are bit-identical
+ * between runs and do not depend on the other dates of the batch.  bounds [T][2],
+ * m0_out / m1_out [T], all host|device. */
+int32_t cvq_slab_moments(cvq_plan* plan, const double* bounds, double* m0_out, double* m1_out,
+                         int32_t mem);
+
+/* No reference counterpart.  Expected Shortfall (CVaR) of a solved VaR vector: with
+ * (m0, m1) the tail moments of (args->lower, var[t] - args->ptf_mean],
+ *   es_out[t] = m1 / m0 + args->ptf_mean,
+ * the mean portfolio return given that it falls at or below the VaR, normalised by the
+ * mass m0 actually found there (not by obj_var: quirks Q1/Q2 do not always leave the
+ * bisection at the obj_var quantile).  NaN where var[t] is NaN (Q3) or m0 == 0.
+ * m0_out [T] receives m0 (may be NULL).  Only lower and ptf_mean of args are read.
+ * var / es_out / m0_out host|device; CVQ_MEM_DEVICE chains behind a device-mode
+ * cvq_solve on the plan's stream without a host synchronisation. */
+int32_t cvq_expected_shortfall(cvq_plan* plan, const cvq_solve_args* args, const double* var,
+                               double* es_out, double* m0_out, int32_t mem);
 
 /* Drop-in for ValueAtRiskCalcualtion.calc_var (calc_var_class.py:95-177 +
  * bisection_algorithm :250-309), quirks Q1-Q4 reproduced.  var_out [T];
