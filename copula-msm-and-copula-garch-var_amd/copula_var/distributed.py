@@ -57,12 +57,14 @@ class ShardedVaR:
     check(): optional convergence check after the finalize (raises on failure).
     es_local(var_block, es_block): optional; Expected Shortfall of this rank's dates from
     their solved VaR (both views of length hi - lo), for expected_shortfall().
+    quant_local(block): optional; exact quantiles of this rank's dates, block [hi - lo, L, 3] =
+    (var, es, m0) per date and level, for quantiles().
     """
 
     def __init__(self, T_total: int, stride: int, local: Callable, finalize: Callable,
                  device: torch.device, group=None, check: Optional[Callable] = None,
                  block_len: Optional[int] = None, hdr_off: Optional[int] = None,
-                 es_local: Optional[Callable] = None):
+                 es_local: Optional[Callable] = None, quant_local: Optional[Callable] = None):
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
@@ -71,6 +73,7 @@ class ShardedVaR:
         self.stride = int(stride)
         self._local, self._finalize, self._check = local, finalize, check
         self._es_local = es_local
+        self._quant_local = quant_local
         if hdr_off is None:                                   # snapshots, padded to 16 B, then the header
             hdr_off = (self.per * self.stride + 1) & ~1
         self.hdr_off = int(hdr_off)
@@ -109,12 +112,25 @@ class ShardedVaR:
         out = blk if not dist.is_initialized() else _gather(blk, self.world, self.group)
         return out[: self.T_total]
 
+    def quantiles(self, L: int) -> torch.Tensor:
+        """Exact quantiles at L levels, [T_total, L, 3] = (var, es, m0) on every rank: each rank
+        fills its own dates into a NaN-padded [per, L, 3] block; one all-gather.  Dates are
+        independent here (no Q2/Q4 coupling), so there is no header exchange and no solve() first."""
+        if self._quant_local is None:
+            raise RuntimeError("this ShardedVaR was built without quant_local")
+        blk = torch.full((self.per, int(L), 3), float("nan"), dtype=torch.float64, device=self.var.device)
+        if self.hi > self.lo:
+            self._quant_local(blk[: self.hi - self.lo])
+        out = blk if not dist.is_initialized() else _gather(blk, self.world, self.group)
+        return out[: self.T_total]
 
-def device_sharded_var(plan, args, T_total: int, device: torch.device, group=None) -> ShardedVaR:
+
+def device_sharded_var(plan, args, T_total: int, device: torch.device, group=None, levels=None) -> ShardedVaR:
     """ShardedVaR wired to a QuadraturePlan's device entry points (plan holds this rank's block).
 
     The plan is bound to torch's current stream at every solve, so its kernels, the
-    snapshot buffers' initialisation and the collectives are ordered on one stream."""
+    snapshot buffers' initialisation and the collectives are ordered on one stream.
+    levels: the levels quantiles(len(levels)) serves through plan.quantiles_device."""
     stride = plan.snap_stride(args)
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     per = shard(T_total, 0, world)[2]
@@ -131,5 +147,12 @@ def device_sharded_var(plan, args, T_total: int, device: torch.device, group=Non
         plan.set_stream(torch.cuda.current_stream(device).cuda_stream)
         plan.expected_shortfall_device(args, var_block.data_ptr(), es_block.data_ptr())
 
+    def quant_local(block):
+        plan.set_stream(torch.cuda.current_stream(device).cuda_stream)
+        out = torch.empty((3,) + tuple(block.shape[:2]), dtype=torch.float64, device=device)   # the ABI's [T][L] arrays
+        plan.quantiles_device(args, levels, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr())
+        block.copy_(out.permute(1, 2, 0))
+
     return ShardedVaR(T_total, stride, local, finalize, device, group, check=plan.solve_status,
-                      block_len=block_len, hdr_off=hdr_off, es_local=es_local)
+                      block_len=block_len, hdr_off=hdr_off, es_local=es_local,
+                      quant_local=quant_local if levels is not None else None)

@@ -190,13 +190,15 @@ class QuadraturePlan:
         if self._wide is not None:
             self._wide.set_stream(stream_handle)
 
-    KERNELS = {"tables": 0, "mass": 1, "solve": 2, "finalize": 3, "slab": 4, "moments": 5}
+    KERNELS = {"tables": 0, "mass": 1, "solve": 2, "finalize": 3, "slab": 4, "moments": 5,
+               "quantiles": 6}
+    MAX_LEVELS = 8                        # CVQ_MAX_LEVELS
 
     def enable_timing(self, on=True) -> None:
         """Record HIP events around kernel launches on the plan's stream: True = every
         kind, False = off, or an iterable of kind names (e.g. ("solve",))."""
         if on is True or on is False:
-            mask = 0x3F if on else 0
+            mask = 0x7F if on else 0
         else:
             mask = 0
             for k in on:
@@ -337,6 +339,33 @@ class QuadraturePlan:
         order behind e.g. solve_device(check=False): no host synchronisation."""
         N.check(N.lib().cvq_expected_shortfall(self._h, C.byref(args), C.c_void_p(var_ptr), C.c_void_p(es_ptr),
                                                C.c_void_p(m0_ptr or 0), N.MEM_DEVICE), "cvq_expected_shortfall")
+
+    # ------------------------------------------------------------ exact quantiles (true VaR and ES)
+    # (no reference counterpart; like the moments they run on this plan whatever its strategy)
+    def quantiles(self, levels, ptf_mean: float = 0.0, min_var=-7.5, max_var=0.0, lower=-100.0,
+                  tolerance=1e-6) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(var, es, m0), each (T, L): per date and level alpha the exact alpha-quantile of the
+        nested-grid measure by plain bisection of F(v) = mass of (lower, v] over (min_var, max_var]
+        (no quirk Q1-Q4; calc_var keeps the reference's result), plus ptf_mean; es and m0 are
+        expected_shortfall's of that var.  NaN var / es where not F(min_var) < alpha <= F(max_var)
+        (m0 = F(max_var) there).  At most MAX_LEVELS levels, each finite and > 0."""
+        lv = N.f64(np.atleast_1d(np.asarray(levels, dtype=np.float64)))
+        if lv.ndim != 1:
+            raise ValueError("levels must be a sequence of numbers")
+        args = solve_args(ptf_mean, min_var=min_var, max_var=max_var, lower=lower, tolerance=tolerance)
+        out = [np.empty((self.T, lv.size)) for _ in range(3)]
+        N.check(N.lib().cvq_quantiles(self._h, C.byref(args), N.ptr(lv), lv.size, N.ptr(out[0]), N.ptr(out[1]),
+                                      N.ptr(out[2]), N.MEM_HOST), "cvq_quantiles")
+        return out[0], out[1], out[2]
+
+    def quantiles_device(self, args: N.CvqSolveArgs, levels, var_ptr: int, es_ptr: Optional[int] = None,
+                         m0_ptr: Optional[int] = None) -> None:
+        """quantiles into device buffers [T][L] (args: min_var, max_var, lower, tolerance and
+        ptf_mean are read; levels stay on the host), in stream order: no host synchronisation."""
+        lv = N.f64(np.atleast_1d(np.asarray(levels, dtype=np.float64)))
+        N.check(N.lib().cvq_quantiles(self._h, C.byref(args), N.ptr(lv), lv.size, C.c_void_p(var_ptr),
+                                      C.c_void_p(es_ptr or 0), C.c_void_p(m0_ptr or 0), N.MEM_DEVICE),
+                "cvq_quantiles")
 
     # ------------------------------------------------------------ device-resident solve
     def solve_device(self, args: N.CvqSolveArgs, var_ptr: int, check: bool = False) -> Optional[int]:

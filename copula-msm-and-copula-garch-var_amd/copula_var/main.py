@@ -61,6 +61,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--plot", default=None, help="PNG of main.py's VaR / returns plot")
     ap.add_argument("--es", action="store_true",
                     help="also compute the Expected Shortfall below each VaR (an <estimation>_es column in --out)")
+    ap.add_argument("--exact-levels", type=float, nargs="+", default=None, metavar="A",
+                    help="also compute the exact quantile (true VaR, without calc_var's reproduced quirks) and its "
+                         "Expected Shortfall at these levels: qvar_<estimation>_<level> / qes_<estimation>_<level> "
+                         "columns in --out")
     return ap
 
 
@@ -70,7 +74,7 @@ def main(argv=None) -> int:
     df = load_returns_csv(a.prices, prices=not a.returns)[a.tickers]
     SharedCacheIndexReturns.returns_cache[(tuple(a.tickers), a.start, a.end)] = df
     weights = np.array(a.weights if a.weights else [1.0 / len(a.tickers)] * len(a.tickers))
-    out, runs, es = {}, {}, {}
+    out, runs, es, exact = {}, {}, {}, {}
     for est in a.estimation:
         calc = ValueAtRiskCalculationFactory.create_var_calculator(copula_type=a.copula, estimation_type=est)
         kw = {"k": a.k} if est == "msm" else {}
@@ -81,6 +85,11 @@ def main(argv=None) -> int:
         if a.es:
             es[est] = runs[est].calc_es(var=out[est])
             print(f"{est}/{a.copula}: mean ES {np.nanmean(es[est]):.4f}", file=sys.stderr)
+        if a.exact_levels:
+            exact[est] = runs[est].calc_quantiles(a.exact_levels)
+            for i, lv in enumerate(a.exact_levels):
+                print(f"{est}/{a.copula}: mean exact VaR at {lv:g}: {np.nanmean(exact[est][0][:, i]):.4f}",
+                      file=sys.stderr)
     first = runs[a.estimation[0]]
     portfolio = first.out_sample_data.mean(axis=1).to_numpy()                    # main.py:73
     if a.out:
@@ -90,6 +99,10 @@ def main(argv=None) -> int:
             cols[f"var_{k}"] = v
             if k in es:
                 cols[f"{k}_es"] = es[k]                     # next to its VaR column
+            if k in exact:
+                for i, lv in enumerate(a.exact_levels):
+                    cols[f"qvar_{k}_{lv:g}"] = exact[k][0][:, i]
+                    cols[f"qes_{k}_{lv:g}"] = exact[k][1][:, i]
         frame = pd.DataFrame(cols, index=idx)
         frame["portfolio_return"] = portfolio[:len(frame)]
         frame.to_csv(a.out)

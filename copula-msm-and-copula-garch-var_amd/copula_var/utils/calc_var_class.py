@@ -133,6 +133,15 @@ class ValueAtRiskCalcualtion:
         es, self.last_tail_mass = self.plan.expected_shortfall(np.asarray(var, dtype=np.float64), self.ptf_mean)
         return es
 
+    def calc_quantiles(self, levels=(0.05,)):
+        """(var, es), each (T, L): the exact quantile of the nested-grid measure at every level
+        (plain bisection, none of calc_var's quirks: where calc_var's result lies above -2 + ptf_mean
+        it is not the obj_var quantile) and the Expected Shortfall below it, all
+        levels in one device call (no reference counterpart).  calc_var stays the reference's
+        number.  The masses found below each quantile are kept in last_tail_mass (T, L)."""
+        var, es, self.last_tail_mass = self.plan.quantiles(levels, self.ptf_mean)
+        return var, es
+
     def compute_integral(self, bounds):
         """I_t(a, b] for every date t (calc_var_class.py:179-212), one device launch."""
         return self.plan.compute_integral(np.asarray(bounds, dtype=np.float64))

@@ -165,7 +165,9 @@ __global__ __launch_bounds__(kMomNT) void k_moments(StaticDev S, const double* _
 
 // One thread per date: its chunks summed in index order.  var == nullptr: out0 = m0, out1 = m1.
 // Else the Expected Shortfall: out1 = m1 / m0 + ptf_mean, NaN where var[t] is NaN (Q3 brackets)
-// or m0 == 0; out0 = m0 (may be nullptr).
+// or m0 == 0; out0 = m0 (may be nullptr).  (Not a template: defined in cvq_moments.hip's
+// translation unit only; cvq_quantile.hip includes this header without it.)
+#ifndef CVQ_NO_MOMENTS_FINISH
 __global__ __launch_bounds__(256) void k_moments_finish(long long T, int chunks, const double* __restrict__ part,
                                                         const double* __restrict__ var, double ptf_mean,
                                                         double* __restrict__ out0, double* __restrict__ out1) {
@@ -183,5 +185,6 @@ __global__ __launch_bounds__(256) void k_moments_finish(long long T, int chunks,
     const double v = var[t];
     out1[t] = (v == v && s0 != 0.0) ? s1 / s0 + ptf_mean : __builtin_nan("");
 }
+#endif
 
 }  // namespace cvq

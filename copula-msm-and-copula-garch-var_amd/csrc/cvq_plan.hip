@@ -152,6 +152,10 @@ struct cvq_plan {
     double* d_mA = nullptr;      // [T][dim][n]
     double* d_mB = nullptr;
     double* d_mpart = nullptr;   // [T][chunks][2]
+    // exact quantiles (cvq_quantiles): per-(date, level) partial sums, state and cuts; the
+    // marginal tables are the moments' d_mA / d_mB
+    size_t capQuant = 0;
+    double* d_qwork = nullptr;
     unsigned long long* d_stamps = nullptr;   // diagnostic phase stamps (CVQ_STAMPS=1)
     bool count_nodes = false;    // cvq_plan_count_nodes: solves record their node counts (stamps)
     bool nodes_valid = false;    // the last solve recorded them
@@ -203,7 +207,8 @@ struct cvq_plan {
 };
 
 namespace {
-enum TimedKernel { TK_TABLES = 0, TK_MASS = 1, TK_SOLVE = 2, TK_FINALIZE = 3, TK_SLAB = 4, TK_MOMENTS = 5, TK_COUNT = 6 };
+enum TimedKernel { TK_TABLES = 0, TK_MASS = 1, TK_SOLVE = 2, TK_FINALIZE = 3, TK_SLAB = 4, TK_MOMENTS = 5, TK_QUANTILES = 6,
+                   TK_COUNT = 7 };
 
 struct TimedScope {
     cvq_plan* p;
@@ -854,6 +859,11 @@ int moments_chunk_count(int dim, int nrows);                                    
 int launch_moments(const StaticDev& S, long long T, hipStream_t stream, const double* a, const double* pi, double* tA,
                    double* tB, double* part, const double* bounds, const double* var, double lower, double ptf_mean,
                    double* out0, double* out1, size_t abi);
+size_t quantile_scratch(int dim, int nrows);                                          // cvq_quantile.hip
+int launch_quantiles(const StaticDev& S, long long T, hipStream_t stream, const double* a, const double* pi,
+                     double* tA, double* tB, double* work, const double* alpha, int L, int K, double min_var,
+                     double max_var, double lower, double ptf_mean, double* var_out, double* es_out, double* m0_out,
+                     size_t abi);
 }
 namespace {
 
@@ -1130,10 +1140,8 @@ int ensure_io(cvq_plan* p, long long need) {
     return CVQ_OK;
 }
 
-// Tail moments: scratch for the current batch, then tables -> partial sums -> per-date sums.
-int run_moments(cvq_plan* p, const double* bounds, const double* var, double lower, double ptf_mean, double* out0,
-                double* out1) {
-    CVQ_HIP_CHECK(hipSetDevice(p->device));
+// Scratch of the tail moments for the current batch (their own tables: solve state untouched).
+int ensure_moments(cvq_plan* p) {
     if (p->T > p->capMom) {
         const size_t tab = (size_t)p->T * p->S.dim * p->S.n;
         const size_t part = (size_t)p->T * moments_chunk_count(p->S.dim, p->S.nrows) * 2;
@@ -1143,9 +1151,35 @@ int run_moments(cvq_plan* p, const double* bounds, const double* var, double low
             return rc;
         p->capMom = p->T;
     }
+    return CVQ_OK;
+}
+
+// Tail moments: scratch for the current batch, then tables -> partial sums -> per-date sums.
+int run_moments(cvq_plan* p, const double* bounds, const double* var, double lower, double ptf_mean, double* out0,
+                double* out1) {
+    CVQ_HIP_CHECK(hipSetDevice(p->device));
+    int rc = ensure_moments(p);
+    if (rc) return rc;
     TimedScope ts(p, TK_MOMENTS);
     return launch_moments(p->S, p->T, p->stream, p->in_a, p->in_pi, p->d_mA, p->d_mB, p->d_mpart, bounds, var, lower,
                           ptf_mean, out0, out1, kernel_abi_key());
+}
+
+// Exact quantiles: the moments' table scratch + their own work buffer, then the pass schedule.
+int run_quantiles(cvq_plan* p, const cvq_solve_args& a, int K, const double* levels, int L, double* var,
+                  double* es, double* m0) {
+    CVQ_HIP_CHECK(hipSetDevice(p->device));
+    int rc = ensure_moments(p);
+    if (rc) return rc;
+    const size_t need = (size_t)p->T * L * quantile_scratch(p->S.dim, p->S.nrows);
+    if (need > p->capQuant) {
+        p->capQuant = 0;
+        if ((rc = dev_alloc(&p->d_qwork, need))) return rc;
+        p->capQuant = need;
+    }
+    TimedScope ts(p, TK_QUANTILES);
+    return launch_quantiles(p->S, p->T, p->stream, p->in_a, p->in_pi, p->d_mA, p->d_mB, p->d_qwork, levels, L, K,
+                            a.min_var, a.max_var, a.lower, a.ptf_mean, var, es, m0, kernel_abi_key());
 }
 
 // Invert a symmetric dim x dim matrix (2 or 3) by cofactors; returns det.
@@ -1170,7 +1204,7 @@ double invert(const double* R, int d, double* Ri) {
 extern "C" {
 
 const char* cvq_last_error(void) { return g_err.c_str(); }
-int32_t cvq_version(void) { return 10100; }
+int32_t cvq_version(void) { return 10200; }
 
 int32_t cvq_device_count(int32_t* count) {
     CVQ_REQUIRE(count != nullptr, CVQ_ERR_INVALID, "count is NULL");
@@ -1411,7 +1445,7 @@ int32_t cvq_plan_destroy(cvq_plan* p) {
     for (void* b : {(void*)p->d_x, (void*)p->d_F, (void*)p->d_phi, (void*)p->d_uvs, (void*)p->d_cf, (void*)p->d_kmax,
                     (void*)p->d_off, (void*)p->d_a, (void*)p->d_pi, (void*)p->d_tA, (void*)p->d_tB,
                     (void*)p->d_C, (void*)p->d_snap, (void*)p->d_hdr, (void*)p->d_err, (void*)p->d_io, (void*)p->d_stamps,
-                    (void*)p->d_mA, (void*)p->d_mB, (void*)p->d_mpart,
+                    (void*)p->d_mA, (void*)p->d_mB, (void*)p->d_mpart, (void*)p->d_qwork,
                     (void*)p->d_cutfix, (void*)p->d_kcut, (void*)p->d_fpair, (void*)p->d_ccount, (void*)p->d_tlist, (void*)p->d_tvs, (void*)p->d_defer, (void*)p->d_vstar, (void*)p->d_bucket, (void*)p->d_sidx, (void*)p->d_svs,
                     (void*)p->d_tree, (void*)p->d_pass,
                     (void*)p->d_pidx, (void*)p->d_pvs})
@@ -1625,6 +1659,40 @@ int32_t cvq_expected_shortfall(cvq_plan* p, const cvq_solve_args* a, const doubl
     if (m0_out)
         CVQ_HIP_CHECK(hipMemcpyAsync(m0_out, p->d_io + T, T * sizeof(double), hipMemcpyDeviceToHost, p->stream));
     CVQ_HIP_CHECK(hipMemcpyAsync(es_out, p->d_io + 2 * T, T * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    CVQ_HIP_CHECK(hipStreamSynchronize(p->stream));
+    return CVQ_OK;
+}
+
+int32_t cvq_quantiles(cvq_plan* p, const cvq_solve_args* a, const double* levels, int32_t n_levels, double* var_out,
+                      double* es_out, double* m0_out, int32_t mem) {
+    cvq::DeviceScope device_scope;                 // the caller's current device, restored on return
+    // arguments first, the plan last: all of it is checked on the host before any device work
+    CVQ_REQUIRE(a != nullptr && levels != nullptr && var_out != nullptr, CVQ_ERR_INVALID, "NULL argument");
+    CVQ_REQUIRE(n_levels >= 1 && n_levels <= CVQ_MAX_LEVELS, CVQ_ERR_INVALID, "n_levels must be in [1, CVQ_MAX_LEVELS]");
+    for (int l = 0; l < n_levels; ++l)
+        CVQ_REQUIRE(levels[l] > 0.0 && std::isfinite(levels[l]), CVQ_ERR_INVALID, "a level must be finite and > 0");
+    CVQ_REQUIRE(std::isfinite(a->min_var) && std::isfinite(a->max_var) && a->max_var > a->min_var, CVQ_ERR_INVALID,
+                "max_var must be above min_var");
+    CVQ_REQUIRE(a->tolerance > 0.0 && std::isfinite(a->tolerance), CVQ_ERR_INVALID, "tolerance must be > 0");
+    CVQ_REQUIRE(!(a->lower > a->min_var) && std::isfinite(a->ptf_mean), CVQ_ERR_INVALID,
+                "lower must not be above min_var; ptf_mean must be finite");
+    const double steps = std::ceil(std::log2((a->max_var - a->min_var) / a->tolerance));
+    CVQ_REQUIRE(steps <= (double)kMaxIters, CVQ_ERR_UNSUPPORTED, "bisection needs more than 62 iterations");
+    const int K = steps > 0.0 ? (int)steps : 0;
+    CVQ_REQUIRE(p != nullptr, CVQ_ERR_INVALID, "plan is NULL");
+    CVQ_REQUIRE(p->T > 0, CVQ_ERR_STATE, "cvq_set_dates must be called first");
+    if (mem == CVQ_MEM_DEVICE) return run_quantiles(p, *a, K, levels, n_levels, var_out, es_out, m0_out);
+    const long long TL = p->T * n_levels;
+    int rc = ensure_io(p, 3 * TL);
+    if (rc) return rc;
+    CVQ_HIP_CHECK(hipSetDevice(p->device));
+    double* d_es = (es_out || m0_out) ? p->d_io + TL : nullptr;       // es is needed for m0's pass anyway
+    if ((rc = run_quantiles(p, *a, K, levels, n_levels, p->d_io, d_es, m0_out ? p->d_io + 2 * TL : nullptr))) return rc;
+    CVQ_HIP_CHECK(hipMemcpyAsync(var_out, p->d_io, TL * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    if (es_out)
+        CVQ_HIP_CHECK(hipMemcpyAsync(es_out, p->d_io + TL, TL * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    if (m0_out)
+        CVQ_HIP_CHECK(hipMemcpyAsync(m0_out, p->d_io + 2 * TL, TL * sizeof(double), hipMemcpyDeviceToHost, p->stream));
     CVQ_HIP_CHECK(hipStreamSynchronize(p->stream));
     return CVQ_OK;
 }

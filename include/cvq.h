@@ -111,8 +111,9 @@ int32_t cvq_plan_info(const cvq_plan* plan, int64_t* reach_nodes, int32_t* rows)
 /* Per-kernel timing with HIP events recorded on the plan's stream (bench.py's
  * live roofline).  kind: 0 tables, 1 joint-mass/prefix, 2 solve, 3 finalize,
  * 4 slab, 5 tail moments (cvq_slab_moments / cvq_expected_shortfall: their tables,
- * partial sums and finish together).  cvq_plan_timing(mask) times the kinds whose
- * bit (1 << kind) is set (0 = off, 0x3F = all) and clears previous records. */
+ * partial sums and finish together), 6 exact quantiles (cvq_quantiles: its tables, passes
+ * and updates together).  cvq_plan_timing(mask) times the kinds whose bit (1 << kind) is
+ * set (0 = off, 0x7F = all) and clears previous records. */
 int32_t cvq_plan_timing(cvq_plan* plan, int32_t enable);
 int32_t cvq_plan_kernel_time(cvq_plan* plan, int32_t kind, double* total_ms, int32_t* launches);
 /* Diagnostic build aid: per-date phase timestamps (s_memtime) of the last DIRECT
@@ -178,6 +179,31 @@ int32_t cvq_slab_moments(cvq_plan* plan, const double* bounds, double* m0_out, d
  * cvq_solve on the plan's stream without a host synchronisation. */
 int32_t cvq_expected_shortfall(cvq_plan* plan, const cvq_solve_args* args, const double* var,
                                double* es_out, double* m0_out, int32_t mem);
+
+/* No reference counterpart.  Exact quantiles of the nested-grid measure at up to CVQ_MAX_LEVELS
+ * levels per date: the true VaR that cvq_solve's reproduced quirk Q1 misses wherever the
+ * quantile lies in (-2, 0], and the Expected Shortfall below it.  With
+ *   F(v) = cvq_slab_moments' m0 of (args->lower, v],
+ *   K = ceil(log2((max_var - min_var) / tolerance))   (23 by default; > 62: CVQ_ERR_UNSUPPORTED),
+ * per date t and level alpha = levels[l]:
+ *   not (F(min_var) < alpha <= F(max_var)):  var = es = NaN, m0 = F(max_var);
+ *   else K steps from (lo, hi) = (min_var, max_var): mid = (lo + hi) / 2, lo = mid if
+ *   F(mid) < alpha else hi = mid (the reference's own update rule, without Q1-Q4);
+ *   var = (lo + hi) / 2 + ptf_mean; es, m0 = cvq_expected_shortfall's of that var.
+ * F is not normalised (quirks Q5/Q6 are the measure's): any finite alpha > 0 is a level.
+ * The node evaluation is shared: the marginal tables are built once per call, the opening
+ * pass (min_var, max_var and the first three steps' seven mids, all level-independent) serves
+ * every level, and each later pass takes three bisection steps (seven cut points) in one sweep
+ * over the nodes of its bracket.  Dates are independent (no Q2/Q4 coupling); each date is a
+ * fixed-order sum: results are bit-identical between runs, across batches and across the
+ * number of levels asked for.  Runs on every strategy with no v_cap limit, on scratch of its
+ * own: the plan's solve state is untouched.  Reads only min_var, max_var, lower, tolerance and
+ * ptf_mean of args.  levels: host [n_levels] whatever `mem` says; var_out / es_out / m0_out
+ * [T][n_levels] host|device, the last two may be NULL.  CVQ_ERR_INVALID: NULL argument,
+ * n_levels outside 1..CVQ_MAX_LEVELS, a level <= 0 or NaN, max_var <= min_var. */
+#define CVQ_MAX_LEVELS 8
+int32_t cvq_quantiles(cvq_plan* plan, const cvq_solve_args* args, const double* levels, int32_t n_levels,
+                      double* var_out, double* es_out, double* m0_out, int32_t mem);
 
 /* Drop-in for ValueAtRiskCalcualtion.calc_var (calc_var_class.py:95-177 +
  * bisection_algorithm :250-309), quirks Q1-Q4 reproduced.  var_out [T];
