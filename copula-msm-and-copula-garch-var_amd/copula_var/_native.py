@@ -26,11 +26,12 @@ CVQ_ERR_RANGE = -6
 CVQ_ERR_NUMERIC = -7
 
 MEM_HOST, MEM_DEVICE = 0, 1
-GAUSSIAN, STUDENT, PLACKETT = 0, 1, 2
+GAUSSIAN, STUDENT, PLACKETT, GUMBEL, GUMBEL_SURVIVAL = 0, 1, 2, 3, 4
 MSM, GARCH, UKF = 0, 1, 2
 STRATEGY_PREFIX, STRATEGY_DIRECT, STRATEGY_COMPACT, STRATEGY_SORTED, STRATEGY_SWEEP = 0, 1, 2, 3, 4
 
-COPULA_KIND = {"gaussian": GAUSSIAN, "student": STUDENT, "plackett": PLACKETT}
+COPULA_KIND = {"gaussian": GAUSSIAN, "student": STUDENT, "plackett": PLACKETT,
+               "gumbel": GUMBEL, "gumbel_survival": GUMBEL_SURVIVAL}
 MODEL_KIND = {"msm": MSM, "garch": GARCH, "mean_reverting": UKF, "ukf": UKF}
 
 _dp = C.POINTER(C.c_double)

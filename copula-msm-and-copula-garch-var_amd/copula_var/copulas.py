@@ -11,6 +11,7 @@ Semantics follow the reference, including its edge behaviour: Student density
 0 when a quantile is non-finite, so c = 0/0 = NaN at u in {0, 1}
 (student.py:133-141, 164-172); Gaussian has no guard (gaussian.py:105-113);
 Plackett uses the reference's non-standard formula (Q11, plackett.py:66-69).
+The Gumbel family has no reference counterpart.
 """
 from __future__ import annotations
 
@@ -69,3 +70,34 @@ def plackett(cdf, theta):
     den = ((1 + (th - 1) * (u + v)) * (1 + (th - 1) * (1 - u - v))) ** 2
     with np.errstate(invalid="ignore", divide="ignore"):
         return num / den
+
+
+def gumbel_log_density(cdf, theta, survival=False):
+    """log c(u) of the exchangeable Gumbel copula C(u) = exp(-(sum_i (-log u_i)^theta)^(1/theta)),
+    theta >= 1, columns = assets (2 or 3); survival: the 180-degree rotation c(1 - u).
+    With x_i = -log u_i, S = sum x_i^theta, A = S^(1/theta), d = dim:
+        log c = -A + sum x_i + (theta - 1) sum log x_i + (1 - d theta) log A + log poly_d(A)
+        poly_2(A) = A + (theta - 1),  poly_3(A) = A^2 + 3 (theta - 1) A + (theta - 1)(2 theta - 1).
+    NaN where a u_i is not strictly inside (0, 1)."""
+    u = np.asarray(cdf, dtype=np.float64)
+    P, d = u.shape
+    if d not in (2, 3):
+        raise ValueError("the Gumbel copula is implemented for 2 or 3 marginals")
+    th = float(np.asarray(theta).reshape(-1)[0])
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        ell = np.log1p(-u) if survival else np.log(u)
+        ok = np.all((u > 0.0) & (u < 1.0), axis=1)
+        x = -ell
+        lx = np.log(x)
+        logS = np.logaddexp.reduce(th * lx, axis=1)
+        logA = logS / th
+        A = np.exp(logA)
+        poly = A + (th - 1) if d == 2 else A * A + 3 * (th - 1) * A + (th - 1) * (2 * th - 1)
+        lc = -A - np.sum(ell, axis=1) + (th - 1) * np.sum(lx, axis=1) + (1 - d * th) * logA + np.log(poly)
+    return np.where(ok, lc, np.nan)
+
+
+def gumbel(cdf, theta, survival=False):
+    """Pointwise Gumbel (survival=True: survival Gumbel) copula density, (P, d) -> (P,)."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        return np.exp(gumbel_log_density(cdf, theta, survival))

@@ -35,6 +35,7 @@ SORTED_MAX_N = {2: 1024, 3: 255}     # sorted_max_n (cvq_sorted_kernels.h): 2-D 
                                       # i1 in 8); its LDS (9 n doubles + a 16-KB tail) is not the bound
 PREFIX_MAX_N_3D = 64                  # PREFIX solves at most 4096 rows (cvq_plan.hip pick_solve_shape)
 MATERIALISED = ("prefix", "sorted", "sweep")   # strategies that hold only nodes with level <= v_cap
+SORTED_ONLY = ("gumbel", "gumbel_survival")     # copulas with SORTED instances only (cvq_plan_create)
 
 
 def general_power(copula: Optional[str], copula_params=None) -> bool:
@@ -49,19 +50,29 @@ def general_power(copula: Optional[str], copula_params=None) -> bool:
 def auto_strategy(model: str, dim: int, n: Optional[int] = None, copula: Optional[str] = None,
                   copula_params=None) -> str:
     """The measured-fastest strategy per workload (cfg 1-5 on one MI355X)
-    among those that run it: COMPACT for 2-asset MSM (cfg 2: 20.3M vs SORTED 16.4M
-    VaR-dates/s) and for 2-asset GARCH / UKF with an integer-power Student copula (cfg 5:
-    25.2M vs 22.5M since r05's grid-edge fast records), SORTED for the other 2-asset
-    GARCH / UKF copulas (cfg 3 Plackett: 8.1M vs 6.3M; cfg 1 Gaussian: 33.8M vs 26.9M) and
-    for 3 assets (the only strategy that runs the 128^3 grid of cfg 4).  n (num_points)
-    bounds the choice: every 2-D strategy takes n <= 512 (the plan's limit, so a 2-D
-    rule never picks a strategy that fails later), 3-D SORTED n <= 255, 3-D PREFIX n <= 64; no 3-D strategy
-    takes n > 255.  A 2-D grid with 512 < n <= 1024 (the reference takes any num_points,
-    calc_var_class.py:16; main.py:50 suggests raising it) runs on SORTED, whose 1024-thread
-    instance holds it.  SORTED and PREFIX hold the nodes with level <= v_cap only;
-    QuadraturePlan(strategy="auto") routes a query above v_cap to an unrestricted
-    sibling plan (COMPACT in 2-D, SORTED with v_cap at the grid's top in 3-D and for
-    2-D n > 512)."""
+    among those that run it, in the order the rule tests:
+      * the Gumbel copulas: SORTED, the only strategy with instances for them;
+      * 2 assets, 512 < n <= 1024: SORTED, whose 1024-thread instance holds the grid (the
+        reference takes any num_points, calc_var_class.py:16; main.py:50 suggests raising it);
+      * 2 assets, a Student copula with a fitted (non-integer) nu: SORTED (cfg 2 10.7-11.0M vs
+        COMPACT 9.2M VaR-dates/s);
+      * 2-asset MSM, and 2-asset GARCH / UKF with an integer-power Student copula: COMPACT
+        (cfg 2: 20.3M vs SORTED 16.4M; cfg 5: 25.2M vs 22.5M);
+      * the other 2-asset GARCH / UKF copulas: SORTED (cfg 3 Plackett: 8.1M vs 6.3M; cfg 1
+        Gaussian: 33.8M vs 26.9M);
+      * 3 assets: SORTED (the only strategy that runs the 128^3 grid of cfg 4).
+    n (num_points) bounds the choice and an unsupported size raises here, never later in the
+    plan: 2-D n <= 1024 (n <= 512 for every strategy but SORTED), 3-D SORTED n <= 255 (3-D
+    PREFIX takes n <= 64 and is never chosen).  SORTED and PREFIX hold the nodes with level
+    <= v_cap only; QuadraturePlan(strategy="auto") routes a query above v_cap to an
+    unrestricted sibling plan (QuadraturePlan._route: COMPACT in 2-D where the copula has
+    COMPACT instances and n <= 512, else SORTED with v_cap at the grid's top)."""
+    if copula in SORTED_ONLY:
+        if dim not in SORTED_MAX_N:
+            raise ValueError(f"the Gumbel copulas run for 2 or 3 assets, got {dim}")
+        if n is not None and n > SORTED_MAX_N[dim]:
+            raise ValueError(f"{dim}-asset grids support num_points <= {SORTED_MAX_N[dim]} (SORTED), got {n}")
+        return "sorted"
     if dim == 2:
         if n is not None and n > MAX_N:
             if n > SORTED_MAX_N[2]:
@@ -146,8 +157,9 @@ class QuadraturePlan:
     def _route(self, top: float) -> "QuadraturePlan":
         """The plan that serves a query reaching level `top`: this one, or (strategy
         "auto" on a materialised strategy, top > v_cap) an unrestricted sibling --
-        COMPACT in 2-D (its slabs run k_direct, any bounds), SORTED in 3-D with v_cap
-        at the grid's top level -- holding the same per-date inputs."""
+        COMPACT in 2-D (its slabs run k_direct, any bounds), SORTED with v_cap at the grid's
+        top level in 3-D, for 2-D n > 512 and for the SORTED-only (Gumbel) copulas -- holding the
+        same per-date inputs."""
         if not self._auto or self.strategy not in MATERIALISED or not (top > self.v_cap):
             return self
         if self._wide is not None and self._wide.strategy in MATERIALISED and top > self._wide.v_cap:
@@ -155,7 +167,7 @@ class QuadraturePlan:
             self._wide = None
         if self._wide is None:
             model, copula, dim, x, step, dens, combos, w, cp, vs, dev = self._ctor
-            if self.dim == 2 and self._x.size <= MAX_N:
+            if self.dim == 2 and self._x.size <= MAX_N and copula not in SORTED_ONLY:
                 self._wide = QuadraturePlan(model, copula, dim, x, step, dens, combos, w, cp, vol_states=vs,
                                             device=dev, strategy="compact")
             else:

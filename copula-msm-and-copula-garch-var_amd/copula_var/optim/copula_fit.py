@@ -19,7 +19,7 @@ from scipy.linalg import cholesky
 from scipy.optimize import minimize
 
 from .. import _native as N
-from ..copulas import gaussian_from_quantiles, plackett, student_from_quantiles
+from ..copulas import gaussian_from_quantiles, gumbel_log_density, plackett, student_from_quantiles
 
 
 def construct_correlation_matrix(dim, corr_params):
@@ -185,4 +185,54 @@ class PlackettCopulaOptimizer(_IFM):
                            bounds=[(0.1, None)], tol=self.tol, options={"maxiter": self.max_iter})
             if res.fun < best_nll:
                 best_nll, best_theta = res.fun, res.x[0]
+        return {"theta": best_theta, "nll": best_nll, "optimized_params": best_theta}
+
+
+class GumbelCopulaOptimizer(_IFM):
+    """IFM fit of the Gumbel (survival=True: survival Gumbel) copula parameter theta by its
+    closed-form log-density (copulas.gumbel_log_density), as PlackettCopulaOptimizer: there is
+    no quantile transform, so nothing to put on the device.  dim 2 or 3.
+
+    A marginal model's CDF saturates in double precision: an in-sample residual far in a tail
+    comes back as exactly 0 or 1 (a poorly fitted GARCH does this on a handful of days), where
+    the Gumbel density is 0 or infinite and the likelihood undefined.  Such a value stands for
+    one within a rounding step of the boundary, so the marginals are clamped to
+    [EDGE, 1 - EDGE], EDGE = 2^-53 (1 - 2^-53 is the largest double below 1; the same step at
+    both ends keeps the fit symmetric under the rotation u -> 1 - u).  Such a row is kept, not
+    dropped, and it weighs heavily: at u = 2^-53 the Gumbel x = -log u is 36.7 (survival, at
+    1 - 2^-53, likewise), entering the likelihood as x^theta, so one saturated observation pulls
+    theta towards independence unless its partner is extreme too.  That is the honest reading of
+    an observation the marginal model calls all but impossible; a caller who prefers to discard
+    such rows filters them before constructing the optimiser.  A NaN marginal or a density <= 0
+    still fails the fit."""
+
+    BOUNDS = (1.0001, 16.0)            # theta = 1 is independence; the device plan takes theta <= 16
+    EDGE = 2.0 ** -53
+
+    def __init__(self, marginals, densities, survival=False, tol=1e-9, max_iter=5000):
+        super().__init__(marginals, densities, tol, max_iter, device=0)
+        if self.dim not in (2, 3):
+            raise ValueError("the Gumbel copula is implemented for 2 or 3 marginals")
+        self.survival = bool(survival)
+        self._u = np.clip(self.marginals, self.EDGE, 1.0 - self.EDGE)      # NaN stays NaN
+
+    def negative_log_likelihood(self, theta):
+        th = float(np.asarray(theta, dtype=np.float64).reshape(-1)[0])
+        total = self._log_dens + np.sum(gumbel_log_density(self._u, th, self.survival))
+        return -total if np.isfinite(total) else 1e10
+
+    def optimize(self, theta_range=None, method="L-BFGS-B"):
+        """One L-BFGS-B run per starting theta inside BOUNDS; the best NLL wins."""
+        if theta_range is None:
+            theta_range = (1.2, 2.0, 4.0, 9.0)
+        best_nll, best_theta = np.inf, None
+        for initial_theta in theta_range:
+            res = minimize(fun=self.negative_log_likelihood, x0=[float(initial_theta)], method=method,
+                           bounds=[self.BOUNDS], tol=self.tol, options={"maxiter": self.max_iter})
+            nll = self.negative_log_likelihood(res.x)
+            if nll < best_nll:
+                best_nll, best_theta = nll, float(res.x[0])
+        if best_theta is None or best_nll >= 1e10:
+            raise ValueError("Gumbel copula fit: the negative log-likelihood is not finite at any start "
+                             "(a NaN marginal, or a marginal density that is not positive)")
         return {"theta": best_theta, "nll": best_nll, "optimized_params": best_theta}

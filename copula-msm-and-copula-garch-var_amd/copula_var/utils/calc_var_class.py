@@ -33,7 +33,7 @@ from ..engine import QuadraturePlan
 
 
 DEVICE_MODELS = ("msm", "garch", "mean_reverting")
-DEVICE_COPULAS = ("student", "gaussian", "plackett")
+DEVICE_COPULAS = ("student", "gaussian", "plackett", "gumbel", "gumbel_survival")
 
 
 def check_device_adapter(method) -> None:

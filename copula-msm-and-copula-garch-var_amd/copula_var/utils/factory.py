@@ -1,6 +1,8 @@
 """(copula x model) factory -- utils/factory.py:10-31 of the reference, including
-Q17: ('mean_reverting', 'gaussian') maps to the Plackett adapter (factory.py:22-23)."""
+Q17: ('mean_reverting', 'gaussian') maps to the Plackett adapter (factory.py:22-23).
+The Gumbel rows have no reference counterpart."""
 from .model_estimation.copula.gaussian_estimation import GaussianCopulaVaR
+from .model_estimation.copula.gumbel_estimation import GumbelCopulaVaR, GumbelSurvivalCopulaVaR
 from .model_estimation.copula.plackett_estimation import PlackettCopulaVaR
 from .model_estimation.copula.student_estimation import StudentCopulaVaR
 from .model_estimation.model.garch_estimation import GarchEstimation
@@ -17,6 +19,12 @@ _TABLE = {
     ("msm", "plackett"): (PlackettCopulaVaR, MSMEstimation),
     ("garch", "plackett"): (PlackettCopulaVaR, GarchEstimation),
     ("mean_reverting", "plackett"): (PlackettCopulaVaR, MeanRevertingEstimation),
+    ("msm", "gumbel"): (GumbelCopulaVaR, MSMEstimation),
+    ("garch", "gumbel"): (GumbelCopulaVaR, GarchEstimation),
+    ("mean_reverting", "gumbel"): (GumbelCopulaVaR, MeanRevertingEstimation),
+    ("msm", "gumbel_survival"): (GumbelSurvivalCopulaVaR, MSMEstimation),
+    ("garch", "gumbel_survival"): (GumbelSurvivalCopulaVaR, GarchEstimation),
+    ("mean_reverting", "gumbel_survival"): (GumbelSurvivalCopulaVaR, MeanRevertingEstimation),
 }
 
 

@@ -90,7 +90,9 @@ int launch_moments(const StaticDev& S, long long T, hipStream_t stream, const do
     switch (S.copula) {
         case CVQ_GAUSSIAN: moments_cop<CVQ_GAUSSIAN>(L); break;
         case CVQ_STUDENT: moments_cop<CVQ_STUDENT>(L); break;
-        default: moments_cop<CVQ_PLACKETT>(L); break;
+        case CVQ_PLACKETT: moments_cop<CVQ_PLACKETT>(L); break;
+        case CVQ_GUMBEL: moments_cop<CVQ_GUMBEL>(L); break;
+        default: CVQ_REQUIRE(false, CVQ_ERR_INVALID, "unknown copula kind");
     }
     CVQ_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(k_moments_finish, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, stream, T,

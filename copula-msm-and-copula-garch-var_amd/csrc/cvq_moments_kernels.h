@@ -136,7 +136,7 @@ __global__ __launch_bounds__(kMomNT) void k_moments(StaticDev S, const double* _
         }
         RowCtx ctx;
         if (DIM == 2) ctx = make_row<COP, DIM>(S, At[i0], 0.0, Bt[i0]);
-        else ctx = make_row<COP, DIM>(S, At[i0], At[n + i1], Bt[i0] * Bt[n + i1]);   // prod over axes in order
+        else ctx = make_row<COP, DIM>(S, At[i0], At[n + i1], outer_B<COP>(Bt[i0], Bt[n + i1]));   // prod over axes in order
         for (int j = j0; j <= j1; ++j) {          // wave-uniform
             double W = 0.0;
 #pragma unroll

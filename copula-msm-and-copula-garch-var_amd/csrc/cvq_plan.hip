@@ -355,7 +355,8 @@ int launch_direct(cvq_plan* p, const SolveConst& P, int mode, const double* boun
     switch (p->S.copula) {
         case CVQ_GAUSSIAN: launch_direct_c<CVQ_GAUSSIAN>(p, P, mode, bounds, out, snaps, hdr); break;
         case CVQ_STUDENT: launch_direct_c<CVQ_STUDENT>(p, P, mode, bounds, out, snaps, hdr); break;
-        default: launch_direct_c<CVQ_PLACKETT>(p, P, mode, bounds, out, snaps, hdr); break;
+        case CVQ_PLACKETT: launch_direct_c<CVQ_PLACKETT>(p, P, mode, bounds, out, snaps, hdr); break;
+        default: CVQ_REQUIRE(false, CVQ_ERR_UNSUPPORTED, "the Gumbel copulas run on the SORTED strategy");
     }
     CVQ_HIP_CHECK(hipGetLastError());
     return CVQ_OK;
@@ -1029,7 +1030,9 @@ int dispatch_cop(cvq_plan* p, bool tables) {
     switch (p->S.copula) {
         case CVQ_GAUSSIAN: launch_cop<CVQ_GAUSSIAN>(p, tables); break;
         case CVQ_STUDENT: launch_cop<CVQ_STUDENT>(p, tables); break;
-        default: launch_cop<CVQ_PLACKETT>(p, tables); break;
+        case CVQ_PLACKETT: launch_cop<CVQ_PLACKETT>(p, tables); break;
+        // SORTED evaluates the Gumbel tables itself (direct_fused); no k_tables / k_mass instances
+        default: CVQ_REQUIRE(false, CVQ_ERR_UNSUPPORTED, "the Gumbel copulas run on the SORTED strategy");
     }
     CVQ_HIP_CHECK(hipGetLastError());
     return CVQ_OK;
@@ -1204,7 +1207,7 @@ double invert(const double* R, int d, double* Ri) {
 extern "C" {
 
 const char* cvq_last_error(void) { return g_err.c_str(); }
-int32_t cvq_version(void) { return 10200; }
+int32_t cvq_version(void) { return 10300; }
 
 int32_t cvq_device_count(int32_t* count) {
     CVQ_REQUIRE(count != nullptr, CVQ_ERR_INVALID, "count is NULL");
@@ -1220,7 +1223,8 @@ int32_t cvq_plan_create(const cvq_static* s, int32_t device, cvq_plan** out) {
     CVQ_REQUIRE(s != nullptr && out != nullptr, CVQ_ERR_INVALID, "NULL argument");
     *out = nullptr;
     CVQ_REQUIRE(s->model >= CVQ_MSM && s->model <= CVQ_UKF, CVQ_ERR_INVALID, "unknown model kind");
-    CVQ_REQUIRE(s->copula >= CVQ_GAUSSIAN && s->copula <= CVQ_PLACKETT, CVQ_ERR_INVALID, "unknown copula kind");
+    CVQ_REQUIRE(s->copula >= CVQ_GAUSSIAN && s->copula <= CVQ_GUMBEL_SURVIVAL, CVQ_ERR_INVALID, "unknown copula kind");
+    const bool gumbel = s->copula == CVQ_GUMBEL || s->copula == CVQ_GUMBEL_SURVIVAL;
     CVQ_REQUIRE(s->dim == 2 || s->dim == 3, CVQ_ERR_UNSUPPORTED, "dim must be 2 or 3");
     CVQ_REQUIRE(!(s->copula == CVQ_PLACKETT && s->dim != 2), CVQ_ERR_UNSUPPORTED,
                 "Plackett copula is only defined for 2-dimensional marginals (plackett.py:20-21)");
@@ -1244,6 +1248,15 @@ int32_t cvq_plan_create(const cvq_static* s, int32_t device, cvq_plan** out) {
                 CVQ_ERR_UNSUPPORTED, "the DIRECT and COMPACT strategies are built for dim == 2");
     CVQ_REQUIRE(!(s->strategy == CVQ_STRATEGY_SORTED && s->dim == 3 && s->n > 255), CVQ_ERR_UNSUPPORTED,
                 "the SORTED strategy supports num_points <= 255 in 3-D");
+    if (gumbel) {                              // all checked before the device is touched
+        CVQ_REQUIRE(s->n_copula_params == 1, CVQ_ERR_INVALID, "the Gumbel copulas take one parameter (theta)");
+        const double th = s->copula_params[0];
+        CVQ_REQUIRE(th == th && th >= 1.0, CVQ_ERR_INVALID, "Gumbel theta must be >= 1");
+        CVQ_REQUIRE(th <= 16.0, CVQ_ERR_UNSUPPORTED,
+                    "Gumbel theta must be <= 16 (Kendall tau 0.94): beyond it x^theta leaves double range at the grid edges");
+        CVQ_REQUIRE(s->strategy == CVQ_STRATEGY_SORTED, CVQ_ERR_UNSUPPORTED,
+                    "the Gumbel copulas run on the SORTED strategy (CVQ_STRATEGY_SORTED) only");
+    }
     for (int l = 0; l < Q; ++l) {             // create_vol_combinations ij order (msm_estimation.py:384)
         int rem = l;
         for (int d = s->dim - 1; d >= 0; --d) {
@@ -1264,7 +1277,8 @@ int32_t cvq_plan_create(const cvq_static* s, int32_t device, cvq_plan** out) {
     p->hx.assign(s->x_values, s->x_values + s->n);
     StaticDev& S = p->S;
     S.model = s->model;
-    S.copula = s->copula;
+    S.copula = gumbel ? CVQ_GUMBEL : s->copula;    // one kernel kind; survival only rotates the margins
+    S.survival = s->copula == CVQ_GUMBEL_SURVIVAL ? 1 : 0;
     S.dim = s->dim;
     S.n = s->n;
     S.q = s->q;
@@ -1284,6 +1298,8 @@ int32_t cvq_plan_create(const cvq_static* s, int32_t device, cvq_plan** out) {
     const double* cp = s->copula_params;
     if (s->copula == CVQ_PLACKETT) {
         CVQ_REQUIRE(s->n_copula_params >= 1, CVQ_ERR_INVALID, "Plackett needs theta");
+        S.theta = cp[0];
+    } else if (gumbel) {
         S.theta = cp[0];
     } else {
         const int nrho = d * (d - 1) / 2;

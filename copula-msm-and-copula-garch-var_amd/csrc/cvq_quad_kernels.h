@@ -69,6 +69,7 @@ __global__ void k_phi(StaticDev S, const double* __restrict__ uvs, double* __res
 //   u   = marginal CDF  (MSM: sum_s f_t[d,s] Phi(x/sigma_{d,s}); GARCH/UKF: Phi(x/sigma_t,d))
 //   A   = z = t.ppf(u, nu) | norm.ppf(u)        (Plackett: A = u)
 //   B   = pdf / univariate-copula-margin-pdf      (MSM: pdf = 1; Plackett: B = pdf)
+//   Gumbel: A = (-log u)^theta, B = log(pdf (-log u)^(theta-1) / u), with 1 - u for u under survival
 // Layout [T][dim][n], coalesced along i.
 // TAB: the plan has verified direct t.ppf tables (Student only; see stdtrit_tabulated).
 // Marginal CDF value u and density factor of grid index i on axis d, date row td.
@@ -107,6 +108,9 @@ __device__ __forceinline__ void marginal_u(const StaticDev& S, const double* __r
     }
 }
 
+constexpr double kGumbelFloor = 1.0e-300;            // floor of a Gumbel table entry x^theta (table_entry)
+constexpr double kLog2e = 1.4426950408889634;
+
 // NUI > 0 (with TAB): the Student nu is the integer NUI -- quantile tail variable by root_nu,
 // B = pdf (1 + z^2/nu)^((nu+1)/2) / g_uni without divisions (~1 ulp from the reference's
 // arithmetic; the VaR tolerates ~1e-8 relative node noise)
@@ -122,7 +126,18 @@ __device__ __forceinline__ void table_entry(const StaticDev& S, const double* __
         *B_out = isfinite(z) ? (pdf * pw) * S.inv_g_uni : pdf * pos_inf();
         return;
     }
-    if (COP == CVQ_PLACKETT) {
+    if constexpr (COP == CVQ_GUMBEL) {
+        // Gumbel family: x = -log u (survival: -log1p(-u), the rotated margin 1 - u),
+        //   A = x^theta, floored at kGumbelFloor (a sum of A's then never leaves the normal range)
+        //   B = log(pdf x^(theta - 1) / u)  -- a LOG factor: outer_B adds where the other kinds multiply
+        // (the plain factor leaves double range at theta = 16 on the grid's edges).  A dead entry
+        // (u not strictly inside (0, 1), or NaN) is A = NaN, which node_value turns into a 0 node.
+        const bool live = u > 0.0 && u < 1.0;
+        const double l = S.survival ? log1p(-u) : log(u);        // < 0 for every live u
+        const double lx = log(-l);
+        *A_out = live ? fmax(exp(S.theta * lx), kGumbelFloor) : __builtin_nan("");
+        *B_out = live ? (log(pdf) + (S.theta - 1.0) * lx) - l : 0.0;
+    } else if (COP == CVQ_PLACKETT) {
         *A_out = u;
         *B_out = pdf;
     } else {
@@ -172,7 +187,22 @@ template <int COP, bool MSM, int DIM>
 __device__ __forceinline__ double node_value(const StaticDev& S, const RowCtx& r, double zc, double Bc,
                                              double W) {
     double c;
-    if (COP == CVQ_PLACKETT) {
+    if constexpr (COP == CVQ_GUMBEL) {
+        // exp(-A) A^(1 - d theta) poly_d(A) prod_i pdf_i x_i^(theta-1) / u_i, A = (sum_i x_i^theta)^(1/theta),
+        // in logs (table_entry); dead rule for both models: a NaN table entry (dead axis) or a
+        // non-finite value is a node of exactly 0 -- no nan_to_num here, +inf is 0 too
+        // log / exp: log_node / exp_node (~1e-14, branch-free, a fraction of the library pair's
+        // registers: with the library calls the 3-D q = 7 / 8 moment and quantile instances spilled).
+        // A NaN sum never reaches log_node; a NaN or infinite exponent gives a non-finite v, hence 0
+        const double th = S.theta, t1 = th - 1.0;
+        const double Sx = (DIM == 2 ? r.z0 : r.z0 + r.z1) + zc;
+        if (!(Sx == Sx)) return 0.0;
+        const double lA = log_node(Sx) / th;
+        const double Av = exp_node(lA);
+        const double poly = DIM == 2 ? Av + t1 : fma(Av, fma(3.0, t1, Av), t1 * (2.0 * th - 1.0));
+        const double v = (exp_node(fma(1.0 - DIM * th, lA, (r.B + Bc) - Av)) * poly) * W;
+        return isfinite(v) ? v : 0.0;
+    } else if (COP == CVQ_PLACKETT) {
         const double u = r.z0, v = zc, th = S.theta;               // plackett.py:66-69 (Q11)
         const double num = th * (1.0 + (th - 1.0) * (u + v - 2.0 * u * v));
         double den = (1.0 + (th - 1.0) * (u + v)) * (1.0 + (th - 1.0) * (1.0 - u - v));
@@ -204,13 +234,20 @@ __device__ __forceinline__ double node_value(const StaticDev& S, const RowCtx& r
     return nan_to_num(c) * W;                                       // garch_integration_function.py:45-50
 }
 
+// The outer axes' B factors of a 3-D row combined (Gumbel's are logs, table_entry)
+template <int COP>
+__device__ __forceinline__ double outer_B(double b0, double b1) {
+    if constexpr (COP == CVQ_GUMBEL) return b0 + b1;
+    else return b0 * b1;
+}
+
 template <int COP, int DIM>
 __device__ __forceinline__ RowCtx make_row(const StaticDev& S, double z0, double z1, double B) {
     RowCtx r;
     r.z0 = z0;
     r.z1 = z1;
     r.B = B;
-    if (COP == CVQ_PLACKETT) {
+    if (COP == CVQ_PLACKETT || COP == CVQ_GUMBEL) {
         r.p0 = r.p1 = r.p2 = 0.0;
         r.fin = true;
     } else if (DIM == 2) {

@@ -77,7 +77,9 @@ void quant_pass(const QuantLaunch& L) {
     switch (L.S.copula) {
         case CVQ_GAUSSIAN: quant_cop<CVQ_GAUSSIAN, C>(L); break;
         case CVQ_STUDENT: quant_cop<CVQ_STUDENT, C>(L); break;
-        default: quant_cop<CVQ_PLACKETT, C>(L); break;
+        case CVQ_PLACKETT: quant_cop<CVQ_PLACKETT, C>(L); break;
+        case CVQ_GUMBEL: quant_cop<CVQ_GUMBEL, C>(L); break;
+        default: break;                                // launch_quantiles rejects unknown kinds
     }
 }
 
@@ -121,7 +123,9 @@ int launch_quantiles(const StaticDev& S, long long T, hipStream_t stream, const 
     switch (S.copula) {
         case CVQ_GAUSSIAN: if (msm) quant_tables<CVQ_GAUSSIAN, true>(Q); else quant_tables<CVQ_GAUSSIAN, false>(Q); break;
         case CVQ_STUDENT: if (msm) quant_tables<CVQ_STUDENT, true>(Q); else quant_tables<CVQ_STUDENT, false>(Q); break;
-        default: if (msm) quant_tables<CVQ_PLACKETT, true>(Q); else quant_tables<CVQ_PLACKETT, false>(Q); break;
+        case CVQ_PLACKETT: if (msm) quant_tables<CVQ_PLACKETT, true>(Q); else quant_tables<CVQ_PLACKETT, false>(Q); break;
+        case CVQ_GUMBEL: if (msm) quant_tables<CVQ_GUMBEL, true>(Q); else quant_tables<CVQ_GUMBEL, false>(Q); break;
+        default: CVQ_REQUIRE(false, CVQ_ERR_INVALID, "unknown copula kind");
     }
     CVQ_HIP_CHECK(hipGetLastError());
     int left = K;

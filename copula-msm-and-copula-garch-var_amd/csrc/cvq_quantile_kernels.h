@@ -154,7 +154,7 @@ __global__ __launch_bounds__(kMomNT) void k_quant_pass(StaticDev S, const double
         }
         RowCtx ctx;
         if (DIM == 2) ctx = make_row<COP, DIM>(S, At[i0], 0.0, Bt[i0]);
-        else ctx = make_row<COP, DIM>(S, At[i0], At[n + i1], Bt[i0] * Bt[n + i1]);   // prod over axes in order
+        else ctx = make_row<COP, DIM>(S, At[i0], At[n + i1], outer_B<COP>(Bt[i0], Bt[n + i1]));   // prod over axes in order
         for (int k = j0; k <= j1; ++k) {          // wave-uniform trip count
             const int jm = SKEW ? ka + 1 + k : k;               // the column whose membership is tested
             const int j = SKEW ? min(jm, n - 1) : k;            // the column loaded (in the grid)

@@ -26,6 +26,8 @@
 //             per-axis log factors g_c = log(B_c w_c) - Ri_cc z_c^2 / 2 tabulated
 //             in LDS (gaussian.py:105-113 divided by the margins, :56-59)
 //   Student   S0 B'1 B'2 (1 + z^T R^-1 z / nu)^-(nu+d)/2   (student.py:133-141)
+//   Gumbel    2^(sum L_i - A log2(e) + (1 - d theta) log2 A) poly_d(A), A = (sum x_i^theta)^(1/theta), from the
+//             per-axis records (x_i^theta, L_i = log2(pdf_i x_i^(theta-1) / u_i w_i)) (no reference)
 // and otherwise the reference-semantics node (node_value, full W contraction,
 // garch_integration_function.py:45-50 nan_to_num).  3-D: the axis-0 weight
 // factor survives only on the plane i1 == 0 (create_grids.py:169-171, Q6) and
@@ -87,7 +89,9 @@ constexpr int kSortIlp = CVQ_SORT_ILP;                // nodes in flight per thr
 #define CVQ_SORT_ILP_WIDE_ST 1     // 2 spilled 2 VGPRs at 6 waves per SIMD
 #endif
 __host__ __device__ constexpr int sorted_ilp(int cop, int pm, int dim, int nt = 256) {
-    return (cop == CVQ_STUDENT && (pm == 0 || dim == 3)) ? CVQ_SORT_ILP_GEN
+    // (the Gumbel node -- log_node, exp_node, exp2_node7 -- carries the general-power Student
+    // node's temporaries and takes its setting)
+    return ((cop == CVQ_STUDENT && (pm == 0 || dim == 3)) || cop == CVQ_GUMBEL) ? CVQ_SORT_ILP_GEN
          : (cop == CVQ_STUDENT && nt >= 512) ? CVQ_SORT_ILP_WIDE_ST : kSortIlp;
 }
 
@@ -132,6 +136,9 @@ struct SortedGeom {
 
 // exp_node: cvq_special.h (the fast records clamp their logs at kLogFloor, within its domain)
 constexpr double kLogFloor = -1.0e4;
+// the log2 factor of a dead Gumbel record, and the floor of a live one: 2^(3 kGumbelDeadL + ...) is +0
+// by exp2_node7's ldexp, and the sum stays far inside its |x| < 1e9 domain
+constexpr double kGumbelDeadL = -1.0e5;
 // the Gaussian node's exp: the records carry the exponent's terms scaled by log2(e), so the node is
 // 2^E' by exp2_node7 (4.0e-11 relative; no ln2 reduction: two FMAs and a multiply fewer than exp_node7,
 // four FMAs fewer than the degree-9 exp_node).  CVQ_SORT_EXP2=0: unscaled records and exp_node7.
@@ -277,7 +284,10 @@ inline size_t sorted_lds_bytes(int n, int nt, int dim, bool sweep = false, int l
 // (the Student instances with a general power stay at 5: their quantile and node temporaries
 // spill 13-15 VGPRs at 6).  cop / pm = -1: the width rule's generic value.
 __host__ __device__ constexpr int sorted_min_waves(int dim, int nt = 256, int cop = -1, int pm = -1) {
-    return dim == 2 ? ((nt >= 512 && !(cop == CVQ_STUDENT && pm == 0)) ? CVQ_SORT_MIN_WAVES2W : CVQ_SORT_MIN_WAVES2)
+    // (the Gumbel instances take 4 at every width: their table phase -- log, log1p, exp per entry --
+    // and node spill 20-32 VGPRs at 5)
+    return cop == CVQ_GUMBEL ? CVQ_SORT_MIN_WAVES3
+         : dim == 2 ? ((nt >= 512 && !(cop == CVQ_STUDENT && pm == 0)) ? CVQ_SORT_MIN_WAVES2W : CVQ_SORT_MIN_WAVES2)
                     : CVQ_SORT_MIN_WAVES3;
 }
 
@@ -392,7 +402,11 @@ __global__ __launch_bounds__(NT, sorted_min_waves(DIM, NT, COP, PM)) void k_sort
             } else {
                 w = S.F[(size_t)ax * n + i];
             }
-            if (!(COP == CVQ_STUDENT && !MSM && !isfinite(A))) {   // dead entries: below
+            if constexpr (COP == CVQ_GUMBEL) {
+                // a dead entry (A = NaN, both models) gets a +0 record below; a live one needs a
+                // finite log factor and a weight with a finite log
+                if (A == A && !(isfinite(B) && w > 0.0 && w < pos_inf())) bad |= 1;
+            } else if (!(COP == CVQ_STUDENT && !MSM && !isfinite(A))) {   // dead entries: below
                 if (!isfinite(A) || !isfinite(B)) bad |= 1;
                 if (!(B * w > 0.0)) bad |= 1;              // fast records take logs of B w
                 if (!(fabs(A) < 1.0e15)) bad |= 1;         // fast powers / exps need a bounded quadratic form
@@ -472,6 +486,20 @@ __global__ __launch_bounds__(NT, sorted_min_waves(DIM, NT, COP, PM)) void k_sort
                 fr1[R1 * i + 1] = (L * k12) * z;
                 fg1[FG * i] = L * (lg(B * w) + kcc);
             }
+        } else if constexpr (COP == CVQ_GUMBEL) {
+            // (x^theta, log2(pdf x^(theta-1) / u  w)) per axis: the node adds the first parts into
+            // S = A^theta and the second into its exponent.  A dead entry (table_entry: NaN, both
+            // models) is (1, kGumbelDeadL): every node through it is 2^(-1e5 + ...) poly = +0 on the
+            // fast path, the dead rule's exact 0, and the date stays off the generic path
+            const bool dead = !(z == z);
+            auto rl = [&](double wv) { return dead ? kGumbelDeadL : fmax(kLog2e * (B + log(wv)), kGumbelDeadL); };
+            double* r = ax == 0 ? fr0 + 2 * i : ax == DIM - 1 ? fr2 + 2 * i : fr1 + R1 * i;
+            r[0] = dead ? 1.0 : z;
+            r[1] = rl(ax == 0 && DIM == 3 ? arest : w);
+            if (DIM == 3 && ax == 0) {                                       // plane i1 == 0 (Q6)
+                fr0[2 * (n + i)] = dead ? 1.0 : z;
+                fr0[2 * (n + i) + 1] = rl(w);
+            }
         } else if constexpr (COP == CVQ_PLACKETT) {       // rec0 = (-2 u, theta s), rec2 = ((theta - 1) v, s)
             double* r = ax == 0 ? fr0 + 2 * i : fr2 + 2 * i;
             r[0] = ax == 0 ? -2.0 * z : (S.theta - 1.0) * z;
@@ -536,6 +564,9 @@ __global__ __launch_bounds__(NT, sorted_min_waves(DIM, NT, COP, PM)) void k_sort
         y = den == 0.0 ? __builtin_inf() : y;             // num / 0 as IEEE division gives it (num * inf)
         return (num * y) * (A.y * C.y);
     };
+    // Gumbel node constants: 1 / theta, theta - 1, (1 - d theta) log2(e), poly_3's constant term
+    const double gu_ith = 1.0 / S.theta, gu_t1 = S.theta - 1.0, gu_e = (1.0 - DIM * S.theta) * kLog2e,
+                 gu_c3 = (S.theta - 1.0) * (2.0 * S.theta - 1.0);
     auto node_fast = [&](uint32_t c) -> double {
         const double2 A = rd2(rec0(c));
         const double2 C = rd2(rec2(c));
@@ -560,6 +591,23 @@ __global__ __launch_bounds__(NT, sorted_min_waves(DIM, NT, COP, PM)) void k_sort
                 sc = (A.y * Bv.y) * C.y;
             }
             return sc * pow_fast<PM>(b, S.node_m, S.node_ex);
+        } else if constexpr (COP == CVQ_GUMBEL) {
+            // 2^(sum L_i - A log2(e) + (1 - d theta) log2 A) poly_d(A), A = S^(1/theta), S = sum x_i^theta.
+            // A sits in the exponent, so its absolute error is the node's relative error: log A and A
+            // from log_node / exp_node (~1e-14), only the outer exponential from exp2_node7 (4e-11).
+            // No intermediate leaves double range (S >= kGumbelFloor, the exponent is a sum of logs)
+            double Sx = A.x, L = A.y;
+            if constexpr (DIM == 3) {
+                const double2 Bv = rd2(rec1(c));
+                Sx += Bv.x;
+                L += Bv.y;
+            }
+            Sx += C.x;
+            L += C.y;
+            const double lA = log_node(Sx) * gu_ith;
+            const double Av = exp_node(lA);
+            const double poly = DIM == 2 ? Av + gu_t1 : fma(Av, Av + 3.0 * gu_t1, gu_c3);
+            return exp2_node7(fma(gu_e, lA, fma(-kLog2e, Av, L))) * poly;
         } else {                                           // Plackett, 2-D
             return plackett(A, C);
         }
@@ -595,7 +643,7 @@ __global__ __launch_bounds__(NT, sorted_min_waves(DIM, NT, COP, PM)) void k_sort
         }
         RowCtx ctx;
         if constexpr (DIM == 2) ctx = make_row<COP, 2>(S, zg[i0], 0.0, Bg[i0]);
-        else ctx = make_row<COP, 3>(S, zg[i0], zg[n + i1], Bg[i0] * Bg[n + i1]);
+        else ctx = make_row<COP, 3>(S, zg[i0], zg[n + i1], outer_B<COP>(Bg[i0], Bg[n + i1]));
         return node_value<COP, MSM, DIM>(S, ctx, zi, Bi, W);
     };
     // sum of the nodes at sorted positions [p0, p1), strided over the workgroup: the rounds start

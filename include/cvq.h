@@ -39,6 +39,13 @@ extern "C" {
 #define CVQ_GAUSSIAN 0
 #define CVQ_STUDENT  1
 #define CVQ_PLACKETT 2
+/* Gumbel family (no reference counterpart): C(u) = exp(-(sum_i (-log u_i)^theta)^(1/theta)),
+ * upper-tail dependent, and its 180-degree rotation c(1 - u) (survival Gumbel, lower-tail
+ * dependent: the loss tail of a long portfolio).  copula_params = [theta], 1 <= theta <= 16,
+ * dim 2 or 3 (exchangeable), CVQ_STRATEGY_SORTED only.  A node contributes exactly 0 where a
+ * marginal CDF value is not strictly inside (0, 1) or the value is not finite (both models). */
+#define CVQ_GUMBEL          3
+#define CVQ_GUMBEL_SURVIVAL 4
 /* model kinds: utils/model_estimation/model/{msm,garch,mean_reverting}_estimation.py */
 #define CVQ_MSM   0
 #define CVQ_GARCH 1
@@ -62,7 +69,7 @@ typedef struct cvq_plan cvq_plan;
  * consumed by calc_integral.py:8-119. */
 typedef struct cvq_static {
     int32_t model;              /* CVQ_MSM | CVQ_GARCH | CVQ_UKF                        */
-    int32_t copula;             /* CVQ_GAUSSIAN | CVQ_STUDENT | CVQ_PLACKETT            */
+    int32_t copula;             /* CVQ_GAUSSIAN | CVQ_STUDENT | CVQ_PLACKETT | CVQ_GUMBEL[_SURVIVAL] */
     int32_t dim;                /* assets: 2 or 3                                        */
     int32_t n;                  /* num_points                                            */
     int32_t q;                  /* unique vol states per asset (GARCH/UKF: 1)            */
@@ -74,7 +81,7 @@ typedef struct cvq_static {
     const double*  weights;     /* [dim]       host, weights[0] > 0                      */
     const double*  vol_states;  /* [dim][q]    host, MSM unique_vol_states; else NULL    */
     const double*  copula_params; /* packed as copula_integrations_params              */
-    int32_t n_copula_params;    /* Student 1+d(d-1)/2, Gaussian d(d-1)/2, Plackett 1     */
+    int32_t n_copula_params;    /* Student 1+d(d-1)/2, Gaussian d(d-1)/2, Plackett 1, Gumbel 1 */
     int32_t strategy;           /* CVQ_STRATEGY_*                                        */
     double  v_cap;              /* largest portfolio level any query may use (e.g. 0)    */
 } cvq_static;
