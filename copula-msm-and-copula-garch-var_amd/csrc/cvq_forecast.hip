@@ -2042,6 +2042,7 @@ int32_t cvq_msm_marginals(int32_t device, int32_t k, double m0, double sigma, do
 int32_t cvq_garch_forecast(int32_t device, double omega, double alpha, double beta, const double* returns_c,
                            int64_t n_in, int64_t T, double* out, int32_t mem) {
     CVQ_REQUIRE(returns_c && out, CVQ_ERR_INVALID, "NULL argument");
+    CVQ_REQUIRE(n_in >= 1 && T >= 1, CVQ_ERR_INVALID, "n_in and T must be >= 1");   // the kernel reads w[n_in - 1]
     CVQ_REQUIRE(omega > 0 && alpha > 0 && beta > 0 && alpha + beta < 1, CVQ_ERR_INVALID,
                 "GARCH parameters must be positive with alpha + beta < 1 (garch/estimation.py:22-38)");
     CVQ_DEVICE_SCOPE(device);
@@ -2088,6 +2089,7 @@ int32_t cvq_garch_forecast_pq(int32_t device, int32_t p, int32_t q, const double
 int32_t cvq_ukf_forecast(int32_t device, double a, double l, double q, const double* returns_c, int64_t n_in,
                          int64_t T, double* out, int32_t mem) {
     CVQ_REQUIRE(returns_c && out, CVQ_ERR_INVALID, "NULL argument");
+    CVQ_REQUIRE(n_in >= 1 && T >= 1, CVQ_ERR_INVALID, "n_in and T must be >= 1");
     CVQ_DEVICE_SCOPE(device);
     int rc = CVQ_OK;
     DevBuf rin, dout;
