@@ -149,9 +149,9 @@ struct Quad {
 // quad-resident state vector.  v: this lane's SL states (state s = lane_q*SL + j),
 // cv: the matching conditional densities.  Returns the normaliser.  IEEE: normalise
 // by IEEE division, v / tot as calc_prob.py does (the reference-facing filter
-// cvq_msm_filter); else by a hardware reciprocal + two Newton steps (~1 ulp; the
-// blocked end-to-end filter and the likelihoods, where ~1e-16 is far below the 1e-8
-// node noise the VaR tolerates).
+// cvq_msm_filter, also the step-by-step path of cvq_msm_tables); else by a hardware
+// reciprocal + two Newton steps (~1 ulp; the likelihoods, where ~1e-16 is far below the
+// 1e-8 node noise the VaR tolerates).
 template <int K, bool IEEE = false>
 __device__ __forceinline__ double msm_step(double (&v)[Quad<K>::SL], const double (&cv)[Quad<K>::SL],
                                            const MsmParams& P, bool* zero) {
@@ -254,187 +254,6 @@ __global__ __launch_bounds__(256) void k_msm_filter(MsmParamsN PN, const double*
             }
         }
     }
-    if (!active) return;
-    if (bad) atomicOr(err, 1);
-#pragma unroll
-    for (int j = 0; j < SL; ++j) out[t * S + lane_q * SL + j] = v[j];
-}
-
-// ------------------------------------------------------- blocked (time-parallel) filter
-// The filter is linear up to its per-step normalisation: window t's filtered vector is
-// normalise(M_{t+n-1} ... M_t u), M_i = diag(c_i) A, u uniform (calc_prob.py:12-13,
-// :51-69).  Rolling windows share all but one of their steps, so the series is cut into
-// blocks of kBlk steps whose products G_b = M_{(b+1)B-1} ... M_{bB} are formed once
-// (k_msm_gblocks, every block in parallel); window t then runs only its partial first and
-// last blocks as filter steps and crosses the full blocks in between with one dense
-// G_b mat-vec each (k_msm_windows): <= 2B + n/B dependent steps instead of n.  All terms
-// are non-negative, so the reordering is benign (no cancellation): the forecasts agree
-// with the step-by-step filter to ~1e-14 relative.
-//
-// k_msm_gblocks: column j of G_b is the un-normalised filter run from e_j over the block;
-// every step is scaled by the common factor 1 / max_s c_i[s] (the same for all columns,
-// so it cancels on the final normalisation) to keep entries <= 1.  One quad per column.
-template <int K>
-__global__ __launch_bounds__(256) void k_msm_gblocks(MsmParamsN PN, const double* __restrict__ cond,
-                                                     long long cstride, int B, int nfull, double* __restrict__ G,
-                                                     long long gstride, int* err) {
-    constexpr int S = Quad<K>::S, L = Quad<K>::L, SL = Quad<K>::SL;
-    const MsmParams& P = PN.a[blockIdx.y];
-    cond += blockIdx.y * cstride;
-    G += blockIdx.y * gstride;
-    const int col = threadIdx.x / L, lane_q = threadIdx.x % L;
-    const int b = blockIdx.x;
-    if (b >= nfull || col >= S) return;
-    double v[SL];
-#pragma unroll
-    for (int j = 0; j < SL; ++j) v[j] = (lane_q * SL + j == col) ? 1.0 : 0.0;
-    const double* base = cond + (long long)b * B * S + lane_q * SL;
-    bool bad = false;
-    for (int i = 0; i < B; ++i) {
-        double cv[SL], m = 0.0;
-#pragma unroll
-        for (int j = 0; j < SL; ++j) {
-            cv[j] = base[(long long)i * S + j];
-            m = fmax(m, cv[j]);
-        }
-        if (L >= 2) m = fmax(m, quad_xor<1>(m));
-        if (L >= 4) m = fmax(m, quad_xor<2>(m));
-        bad |= !(m > 0.0);                             // every state's density is 0: calc_prob.py:64-65
-        const double s = 1.0 / m;
-#pragma unroll
-        for (int c = 0; c < K; ++c) {
-            const int pos = K - 1 - c;
-            const double pc = P.p[c], qc = P.qv[c];
-            if (pos < Quad<K>::LB) {
-                double nv[SL];
-#pragma unroll
-                for (int j = 0; j < SL; ++j) nv[j] = pc * v[j] + qc * v[j ^ (1 << pos)];
-#pragma unroll
-                for (int j = 0; j < SL; ++j) v[j] = nv[j];
-            } else {
-                const int mm = 1 << (pos - Quad<K>::LB);
-#pragma unroll
-                for (int j = 0; j < SL; ++j) {
-                    const double o = mm == 1 ? quad_xor<1>(v[j]) : quad_xor<2>(v[j]);
-                    v[j] = pc * v[j] + qc * o;
-                }
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < SL; ++j) v[j] = v[j] * (cv[j] * s);
-    }
-    if (bad && col == 0 && lane_q == 0) atomicOr(err, 1);
-    double* g = G + (long long)b * S * S;                       // G_b[r][c], row-major
-#pragma unroll
-    for (int j = 0; j < SL; ++j) g[(lane_q * SL + j) * S + col] = v[j];
-}
-
-// k_msm_windows: one quad per window, kWinPerWG windows per workgroup; the full blocks any
-// of the workgroup's windows crosses are staged in LDS once.
-constexpr int kWinPerWG = 16;
-
-template <int K>
-__device__ __forceinline__ void msm_steps(double (&v)[Quad<K>::SL], const double* __restrict__ base, long long i0,
-                                          long long i1, const MsmParams& P, bool* bad) {
-    constexpr int SL = Quad<K>::SL;
-    constexpr int S = Quad<K>::S;
-    constexpr int PF = 4;                                       // rows in flight ahead of the chain
-    double ring[PF][SL];
-#pragma unroll
-    for (int d = 0; d < PF; ++d)
-#pragma unroll
-        for (int j = 0; j < SL; ++j) ring[d][j] = (i0 + d < i1) ? base[(i0 + d) * S + j] : 0.0;
-    for (long long i = i0; i < i1; i += PF) {
-#pragma unroll
-        for (int d = 0; d < PF; ++d) {
-            if (i + d < i1) {
-                double cv[SL];
-#pragma unroll
-                for (int j = 0; j < SL; ++j) cv[j] = ring[d][j];
-                const long long nx = i + d + PF;
-#pragma unroll
-                for (int j = 0; j < SL; ++j) ring[d][j] = nx < i1 ? base[nx * S + j] : 0.0;
-                bool z;
-                msm_step<K>(v, cv, P, &z);
-                *bad |= z;
-            }
-        }
-    }
-}
-
-template <int K>
-__global__ __launch_bounds__(64) void k_msm_windows(MsmParamsN PN, const double* __restrict__ cond, long long cstride,
-                                                    const double* __restrict__ G, long long gstride, int B,
-                                                    long long n_in, long long T, double* __restrict__ out,
-                                                    long long ostride, int* err) {
-    constexpr int S = Quad<K>::S, L = Quad<K>::L, SL = Quad<K>::SL;
-    static_assert(L == 4 && SL * L == S, "blocked filter: a quad holds the states (2 <= k <= 4)");
-    extern __shared__ __attribute__((aligned(16))) double gl[];       // [nb][S][S]
-    const MsmParams& P = PN.a[blockIdx.y];
-    cond += blockIdx.y * cstride;
-    G += blockIdx.y * gstride;
-    out += blockIdx.y * ostride;
-    const long long t0 = (long long)blockIdx.x * kWinPerWG;
-    const long long tl = min(t0 + kWinPerWG, T) - 1;                  // last window of the workgroup
-    const long long blo = t0 / B + 1, bhi = (tl + n_in - 1) / B - 1;  // full blocks crossed by any window
-    const long long nb = bhi >= blo ? bhi - blo + 1 : 0;
-    {
-        const double2* src = (const double2*)(G + blo * S * S);
-        double2* dst = (double2*)gl;
-        for (long long w = threadIdx.x; w < nb * S * S / 2; w += blockDim.x) dst[w] = src[w];
-    }
-    __syncthreads();
-    const long long t = t0 + threadIdx.x / L;
-    const int lane_q = threadIdx.x % L;
-    const bool active = t < T;
-    const long long tt = active ? t : T - 1;
-    const long long b0 = tt / B, b1 = (tt + n_in - 1) / B;            // b1 >= b0 + 1 (host: n_in > B)
-    double v[SL];
-#pragma unroll
-    for (int j = 0; j < SL; ++j) v[j] = 1.0 / S;                      // equi_prob (calc_prob.py:12-13)
-    bool bad = false;
-    const double* base = cond + lane_q * SL;
-    msm_steps<K>(v, base, tt, (b0 + 1) * B, P, &bad);                 // first partial block
-    for (long long b = b0 + 1; b < b1; ++b) {                         // full blocks: dense mat-vec
-        // the window's whole vector: src[x] = the states of quad lane lane_q ^ x
-        double src[4][SL];
-#pragma unroll
-        for (int j = 0; j < SL; ++j) {
-            src[0][j] = v[j];
-            src[1][j] = quad_xor<1>(v[j]);
-            src[2][j] = quad_xor<2>(v[j]);
-            src[3][j] = quad_xor<1>(src[2][j]);
-        }
-        const double* g = gl + (b - blo) * S * S + lane_q * SL * S;   // this lane's SL rows
-        double part = 0.0;
-#pragma unroll
-        for (int j = 0; j < SL; ++j) {
-            double a0 = 0.0, a1 = 0.0;
-#pragma unroll
-            for (int x = 0; x < 4; ++x) {
-                const double* gp = g + j * S + (lane_q ^ x) * SL;     // columns of lane lane_q ^ x
-                if constexpr (SL == 1) {
-                    a0 = fma(gp[0], src[x][0], a0);
-                } else {
-#pragma unroll
-                    for (int jj = 0; jj < SL; jj += 2) {
-                        const double2 gg = *(const double2*)(gp + jj);
-                        a0 = fma(gg.x, src[x][jj], a0);
-                        a1 = fma(gg.y, src[x][jj + 1], a1);
-                    }
-                }
-            }
-            v[j] = a0 + a1;
-            part += v[j];
-        }
-        double tot = part + quad_xor<1>(part);
-        tot += quad_xor<2>(tot);
-        bad |= !(tot > 0.0);
-        const double inv = 1.0 / tot;
-#pragma unroll
-        for (int j = 0; j < SL; ++j) v[j] *= inv;
-    }
-    msm_steps<K>(v, base, b1 * B, tt + n_in, P, &bad);                // last partial block
     if (!active) return;
     if (bad) atomicOr(err, 1);
 #pragma unroll
@@ -1665,49 +1484,6 @@ int launch_filter_k(int k, const MsmParamsN& P, int dim, const double* cond, lon
     return CVQ_OK;
 }
 
-// Block length of the blocked filter for 2**k states and windows of n_in steps, or 0 for
-// the step-by-step filter (k outside [2, 4], windows not longer than a block, or the
-// full blocks a workgroup's windows cross would not fit kBlockLdsMax of LDS).
-constexpr size_t kBlockLdsMax = 80 * 1024;
-#ifndef CVQ_MSM_BLOCK
-#define CVQ_MSM_BLOCK 32
-#endif
-
-size_t blocked_lds_bytes(int k, long long n_in, int B) {
-    const long long S = 1LL << k;
-    return (size_t)((kWinPerWG - 1 + n_in - 1) / B + 1) * S * S * sizeof(double);
-}
-
-int msm_block_len(int k, long long n_in) {
-    if (k < 2 || k > 4 || CVQ_MSM_BLOCK <= 0) return 0;
-    int B = CVQ_MSM_BLOCK;
-    while (blocked_lds_bytes(k, n_in, B) > kBlockLdsMax) B *= 2;
-    return n_in > B ? B : 0;
-}
-
-template <int K>
-void launch_blocked(const MsmParamsN& P, int dim, const double* cond, long long N, long long n_in, long long T, int B,
-                    double* G, double* out, int* err, hipStream_t stream) {
-    constexpr int S = 1 << K;
-    const long long nfull = N / B;
-    hipLaunchKernelGGL(k_msm_gblocks<K>, dim3((unsigned)nfull, (unsigned)dim), dim3(4 * S), 0, stream, P, cond,
-                       N * S, B, (int)nfull, G, nfull * S * S, err);
-    hipLaunchKernelGGL(k_msm_windows<K>, dim3((unsigned)((T + kWinPerWG - 1) / kWinPerWG), (unsigned)dim),
-                       dim3(4 * kWinPerWG), blocked_lds_bytes(K, n_in, B), stream, P, cond, N * S, G, nfull * S * S,
-                       B, n_in, T, out, T * S, err);
-}
-
-int launch_blocked_k(int k, const MsmParamsN& P, int dim, const double* cond, long long N, long long n_in, long long T,
-                     int B, double* G, double* out, int* err, hipStream_t stream) {
-    switch (k) {
-        case 2: launch_blocked<2>(P, dim, cond, N, n_in, T, B, G, out, err, stream); break;
-        case 3: launch_blocked<3>(P, dim, cond, N, n_in, T, B, G, out, err, stream); break;
-        default: launch_blocked<4>(P, dim, cond, N, n_in, T, B, G, out, err, stream); break;
-    }
-    CVQ_HIP_CHECK(hipGetLastError());
-    return CVQ_OK;
-}
-
 // Transfer-matrix scan filter (k_msm_blkscan -> k_msm_supscan -> k_msm_scanwin): 2 <= k <= 4
 // (one wavefront per superblock scan); k = 5, 6 the wide variant (no stored prefixes, 256-thread
 // superblock scans, one wavefront per window); windows longer than two blocks.
@@ -1805,13 +1581,10 @@ int32_t cvq_msm_tables_scratch(int32_t dim, int32_t k, int64_t n_in, int64_t T, 
     CVQ_REQUIRE(doubles != nullptr, CVQ_ERR_INVALID, "NULL argument");
     CVQ_REQUIRE(dim >= 1 && dim <= 3 && k >= 1 && k <= 7 && n_in >= 1 && T >= 1, CVQ_ERR_INVALID, "bad shape");
     const long long S = 1LL << k, N = n_in + T - 1;
-    long long G;
+    long long G = 0;                                       // the step-by-step filter needs none
     if (msm_scan_ok(k, n_in)) {                            // scan filter: prefixes, suffixes, block / superblock products
         const ScanLayout L = scan_layout(k, n_in, T);
         G = dim * (L.pre + L.suf + L.gf + 2 * L.sup);
-    } else {
-        const int B = msm_block_len(k, n_in);
-        G = B ? dim * (N / B) * S * S : 0;                  // blocked filter: full-block products
     }
     // cond, filtered probabilities, [G], error word (2 doubles), scan filter: per-block error flags
     *doubles = dim * N * S + dim * T * S + G + 2 + (scan_flag_count(k, n_in, T, dim) + 1) / 2;
@@ -1842,18 +1615,17 @@ int32_t cvq_msm_tables(int32_t device, void* stream, int32_t dim, int32_t k, con
     hipStream_t st = (hipStream_t)stream;
     const long long N = n_in + T - 1;
     const bool scan = msm_scan_ok(k, n_in);
-    const int B = scan ? 0 : msm_block_len(k, n_in);
     double* cond = scratch;
     double* filt = cond + (long long)dim * N * S;
     double* G = filt + (long long)dim * T * S;
-    long long gsz = B ? (long long)dim * (N / B) * S * S : 0;
+    long long gsz = 0;
     if (scan) {
         const ScanLayout L = scan_layout(k, n_in, T);
         gsz = dim * (L.pre + L.suf + L.gf + 2 * L.sup);
     }
     int* err = (int*)(G + gsz);
     // the scan filter's blocks overwrite their own error flags (err + 4 ...) on every run; the
-    // step-by-step and blocked filters OR into the error word, reset here
+    // step-by-step filter ORs into the error word, reset here
     if (!scan) CVQ_HIP_CHECK(hipMemsetAsync(err, 0, sizeof(int), st));
     if (scan) {                        // densities computed per block inside; the collapse fused into the windows
         StateMapQ MQ{};                                  // k <= 4: <= 16 states
@@ -1871,8 +1643,7 @@ int32_t cvq_msm_tables(int32_t device, void* stream, int32_t dim, int32_t k, con
     } else {
         hipLaunchKernelGGL(k_msm_cond, dim3((unsigned)((N * S + 255) / 256), (unsigned)dim), dim3(256), 0, st, P, S,
                            returns_c, N, cond);
-        if (B) rc = launch_blocked_k(k, P, dim, cond, N, n_in, T, B, G, filt, err, st);
-        else rc = launch_filter_k(k, P, dim, cond, N, n_in, T, filt, err, st);
+        rc = launch_filter_k(k, P, dim, cond, N, n_in, T, filt, err, st);
         if (rc) return rc;
         hipLaunchKernelGGL(k_msm_fbs, dim3((unsigned)((T * dim + 255) / 256)), dim3(256), 0, st, M, dim, S, q, filt,
                            T, fbs_out);
@@ -1886,13 +1657,10 @@ int32_t cvq_msm_tables(int32_t device, void* stream, int32_t dim, int32_t k, con
 int32_t cvq_msm_tables_status(double* scratch, int32_t dim, int32_t k, int64_t n_in, int64_t T, void* stream) {
     CVQ_REQUIRE(scratch != nullptr, CVQ_ERR_INVALID, "NULL argument");
     const long long S = 1LL << k, N = n_in + T - 1;
-    long long G;
+    long long G = 0;
     if (msm_scan_ok(k, n_in)) {
         const ScanLayout L = scan_layout(k, n_in, T);
         G = dim * (L.pre + L.suf + L.gf + 2 * L.sup);
-    } else {
-        const int B = msm_block_len(k, n_in);
-        G = B ? dim * (N / B) * S * S : 0;
     }
     int e = 0;
     const int* err = (const int*)(scratch + dim * N * S + dim * T * S + G);

@@ -141,8 +141,8 @@ def test_device_sigma_tables_ukf_failure_is_reported():
 
 def test_device_tables_zero_normaliser_is_reported():
     """A return so extreme that every state's density underflows to 0 makes the reference's
-    Bayes normaliser 0 (calc_prob.py:64-65): the device stage flags it (blocked filter:
-    in the block products and the window steps) and status() raises."""
+    Bayes normaliser 0 (calc_prob.py:64-65): the device stage flags it (k = 4, n_in = 300 is the
+    narrow scan filter: the per-block flag of the block that holds the return) and status() raises."""
     from copula_var import _native as N
     c_params = [{"m_0": 0.45, "sig": 1.2, "b": 3.0, "gamma": 0.3}, {"m_0": 0.5, "sig": 1.2, "b": 3.0, "gamma": 0.3}]
     n_in, T = 300, 40
@@ -153,10 +153,10 @@ def test_device_tables_zero_normaliser_is_reported():
 
 
 @pytest.mark.parametrize("n_in,T", [(33, 7), (64, 100), (1135, 1000), (3000, 50)])
-def test_blocked_filter_matches_stepwise(n_in, T):
-    """The blocked filter (block products + partial-block steps) against the step-by-step
-    device filter on every window, across block-length regimes (n_in just above one
-    block, several, the cfg-2 geometry, and long windows that double the block)."""
+def test_narrow_scan_filter_matches_stepwise(n_in, T):
+    """The narrow scan filter (k = 4, n_in > 32: k_msm_blkscan, k_msm_supscan, k_msm_scanwin)
+    against the step-by-step device filter cvq_msm_filter on every window, from n_in just above
+    the scan's threshold over the cfg-2 geometry to windows of 3000 steps (24 superblocks)."""
     from copula_var import engine
     p = {"m_0": 0.45, "sig": 1.2, "b": 3.0, "gamma": 0.3}
     rc = np.random.default_rng(11).standard_normal((n_in + T - 1, 2)) * 1.1
