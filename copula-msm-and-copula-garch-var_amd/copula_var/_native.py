@@ -85,6 +85,8 @@ def _declare(lib: C.CDLL) -> None:
         "cvq_slab": (i32, [v, v, v, i32]),
         "cvq_slab_moments": (i32, [v, v, v, v, i32]),
         "cvq_expected_shortfall": (i32, [v, C.POINTER(CvqSolveArgs), v, v, v, i32]),
+        "cvq_slab_axis_moments": (i32, [v, v, v, v, i32]),
+        "cvq_es_contributions": (i32, [v, C.POINTER(CvqSolveArgs), v, v, v, i32]),
         "cvq_quantiles": (i32, [v, C.POINTER(CvqSolveArgs), v, i32, v, v, v, i32]),
         "cvq_solve": (i32, [v, C.POINTER(CvqSolveArgs), v, _ip, i32]),
         "cvq_snap_stride": (i32, [C.POINTER(CvqSolveArgs), _ip]),

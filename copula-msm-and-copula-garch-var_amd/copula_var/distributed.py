@@ -59,12 +59,16 @@ class ShardedVaR:
     their solved VaR (both views of length hi - lo), for expected_shortfall().
     quant_local(block): optional; exact quantiles of this rank's dates, block [hi - lo, L, 3] =
     (var, es, m0) per date and level, for quantiles().
+    contrib_local(var_block, contrib_block): optional; per-asset ES contributions of this rank's
+    dates from their solved VaR (views [hi - lo] and [hi - lo, dim]), for es_contributions();
+    dim: the number of assets (columns of that block).
     """
 
     def __init__(self, T_total: int, stride: int, local: Callable, finalize: Callable,
                  device: torch.device, group=None, check: Optional[Callable] = None,
                  block_len: Optional[int] = None, hdr_off: Optional[int] = None,
-                 es_local: Optional[Callable] = None, quant_local: Optional[Callable] = None):
+                 es_local: Optional[Callable] = None, quant_local: Optional[Callable] = None,
+                 contrib_local: Optional[Callable] = None, dim: Optional[int] = None):
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
@@ -74,6 +78,7 @@ class ShardedVaR:
         self._local, self._finalize, self._check = local, finalize, check
         self._es_local = es_local
         self._quant_local = quant_local
+        self._contrib_local, self.dim = contrib_local, dim
         if hdr_off is None:                                   # snapshots, padded to 16 B, then the header
             hdr_off = (self.per * self.stride + 1) & ~1
         self.hdr_off = int(hdr_off)
@@ -112,6 +117,17 @@ class ShardedVaR:
         out = blk if not dist.is_initialized() else _gather(blk, self.world, self.group)
         return out[: self.T_total]
 
+    def es_contributions(self) -> torch.Tensor:
+        """Per-asset ES contributions [T_total, dim] on every rank, after solve(): each rank fills
+        its own dates from var[lo:hi] into a NaN-padded [per, dim] block; one all-gather."""
+        if self._contrib_local is None or self.dim is None:
+            raise RuntimeError("this ShardedVaR was built without contrib_local (and dim)")
+        blk = torch.full((self.per, int(self.dim)), float("nan"), dtype=torch.float64, device=self.var.device)
+        if self.hi > self.lo:
+            self._contrib_local(self.var[self.lo:self.hi], blk[: self.hi - self.lo])
+        out = blk if not dist.is_initialized() else _gather(blk, self.world, self.group)
+        return out[: self.T_total]
+
     def quantiles(self, L: int) -> torch.Tensor:
         """Exact quantiles at L levels, [T_total, L, 3] = (var, es, m0) on every rank: each rank
         fills its own dates into a NaN-padded [per, L, 3] block; one all-gather.  Dates are
@@ -147,6 +163,10 @@ def device_sharded_var(plan, args, T_total: int, device: torch.device, group=Non
         plan.set_stream(torch.cuda.current_stream(device).cuda_stream)
         plan.expected_shortfall_device(args, var_block.data_ptr(), es_block.data_ptr())
 
+    def contrib_local(var_block, contrib_block):
+        plan.set_stream(torch.cuda.current_stream(device).cuda_stream)
+        plan.es_contributions_device(args, var_block.data_ptr(), contrib_block.data_ptr())
+
     def quant_local(block):
         plan.set_stream(torch.cuda.current_stream(device).cuda_stream)
         out = torch.empty((3,) + tuple(block.shape[:2]), dtype=torch.float64, device=device)   # the ABI's [T][L] arrays
@@ -155,4 +175,5 @@ def device_sharded_var(plan, args, T_total: int, device: torch.device, group=Non
 
     return ShardedVaR(T_total, stride, local, finalize, device, group, check=plan.solve_status,
                       block_len=block_len, hdr_off=hdr_off, es_local=es_local,
-                      quant_local=quant_local if levels is not None else None)
+                      quant_local=quant_local if levels is not None else None,
+                      contrib_local=contrib_local, dim=plan.dim)

@@ -352,6 +352,74 @@ class QuadraturePlan:
         N.check(N.lib().cvq_expected_shortfall(self._h, C.byref(args), C.c_void_p(var_ptr), C.c_void_p(es_ptr),
                                                C.c_void_p(m0_ptr or 0), N.MEM_DEVICE), "cvq_expected_shortfall")
 
+    # ------------------------------------------------------------ risk attribution (Euler contributions)
+    # (no reference counterpart; like the moments they run on this plan whatever its strategy)
+    @property
+    def axis_weights(self) -> np.ndarray:
+        """wa (dim,): the weight the membership rule gives grid axis c, i.e. asset c in input
+        order -- wa[dim-1] = weights[0], wa[c] = weights[c+1] for c < dim-1 (quirk Q10: weights[k]
+        is NOT asset k's weight unless the weights are equal)."""
+        return np.concatenate((self._w[1:self.dim], self._w[:1]))
+
+    def axis_moments(self, bounds) -> Tuple[np.ndarray, np.ndarray]:
+        """(m0 (T,), mx (T, dim)) of the slab (bounds[t, 0], bounds[t, 1]]: m0 = tail_moments' m0
+        bit for bit, mx[:, c] = sum of x[i_c] x mass (axis c = asset c);
+        mx @ axis_weights = tail_moments' m1 to rounding."""
+        b = N.f64(bounds)
+        if b.shape != (self.T, 2):
+            raise ValueError(f"bounds must have shape ({self.T}, 2)")
+        m0, mx = np.empty(self.T), np.empty((self.T, self.dim))
+        N.check(N.lib().cvq_slab_axis_moments(self._h, N.ptr(b), N.ptr(m0), N.ptr(mx), N.MEM_HOST),
+                "cvq_slab_axis_moments")
+        return m0, mx
+
+    def axis_moments_device(self, bounds_ptr: int, m0_ptr: int, mx_ptr: int) -> None:
+        """axis_moments on device buffers (mx [T][dim]), in stream order (no host synchronisation)."""
+        N.check(N.lib().cvq_slab_axis_moments(self._h, C.c_void_p(bounds_ptr), C.c_void_p(m0_ptr),
+                                              C.c_void_p(mx_ptr), N.MEM_DEVICE), "cvq_slab_axis_moments")
+
+    def es_contributions(self, var, ptf_mean: float = 0.0, lower: float = -100.0) -> Tuple[np.ndarray, np.ndarray]:
+        """(contrib (T, dim), m0 (T,)) for a solved VaR vector: the Euler allocation of the ES,
+        contrib[t, c] = axis_weights[c] * E[x_c | portfolio <= VaR] over (lower, var - ptf_mean].
+        A row sums to es - ptf_mean (ptf_mean is not allocated); NaN rows where var is NaN or
+        m0 == 0, as expected_shortfall."""
+        v = N.f64(var)
+        if v.shape != (self.T,):
+            raise ValueError(f"var must have shape ({self.T},)")
+        args = solve_args(ptf_mean, lower=lower)
+        contrib, m0 = np.empty((self.T, self.dim)), np.empty(self.T)
+        N.check(N.lib().cvq_es_contributions(self._h, C.byref(args), N.ptr(v), N.ptr(contrib), N.ptr(m0),
+                                             N.MEM_HOST), "cvq_es_contributions")
+        return contrib, m0
+
+    def es_contributions_device(self, args: N.CvqSolveArgs, var_ptr: int, contrib_ptr: int,
+                                m0_ptr: Optional[int] = None) -> None:
+        """es_contributions on device buffers (contrib [T][dim]; args: lower and ptf_mean are
+        read), in stream order behind solve_device / expected_shortfall_device: no host
+        synchronisation."""
+        N.check(N.lib().cvq_es_contributions(self._h, C.byref(args), C.c_void_p(var_ptr), C.c_void_p(contrib_ptr),
+                                             C.c_void_p(m0_ptr or 0), N.MEM_DEVICE), "cvq_es_contributions")
+
+    def var_contributions(self, var, ptf_mean: float = 0.0, band: float = 0.25
+                          ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(contrib (T, dim), band_mean (T,), m0 (T,)): the discrete-grid estimate of
+        axis_weights[c] * E[x_c | L = VaR], the Euler allocation of the VaR, as the same ratio
+        over the band (var - ptf_mean - band, var - ptf_mean].  A row sums to band_mean, the
+        band's mean level (inside the band, not the VaR itself); NaN rows where var is NaN or the
+        band holds no mass."""
+        v = N.f64(var)
+        if v.shape != (self.T,):
+            raise ValueError(f"var must have shape ({self.T},)")
+        if not band > 0.0:
+            raise ValueError("band must be > 0")
+        top = v - ptf_mean
+        m0, mx = self.axis_moments(np.column_stack((top - band, top)))
+        ok = ~np.isnan(v) & (m0 != 0.0)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            contrib = np.where(ok[:, None], self.axis_weights * mx / m0[:, None], np.nan)
+            band_mean = np.where(ok, (mx @ self.axis_weights) / m0, np.nan)
+        return contrib, band_mean, m0
+
     # ------------------------------------------------------------ exact quantiles (true VaR and ES)
     # (no reference counterpart; like the moments they run on this plan whatever its strategy)
     def quantiles(self, levels, ptf_mean: float = 0.0, min_var=-7.5, max_var=0.0, lower=-100.0,

@@ -61,6 +61,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--plot", default=None, help="PNG of main.py's VaR / returns plot")
     ap.add_argument("--es", action="store_true",
                     help="also compute the Expected Shortfall below each VaR (an <estimation>_es column in --out)")
+    ap.add_argument("--contributions", action="store_true",
+                    help="also compute each asset's Euler contribution to the Expected Shortfall (implies --es; "
+                         "<estimation>_esc_<ticker> columns in --out, summing to <estimation>_es minus the "
+                         "portfolio mean)")
     ap.add_argument("--exact-levels", type=float, nargs="+", default=None, metavar="A",
                     help="also compute the exact quantile (true VaR, without calc_var's reproduced quirks) and its "
                          "Expected Shortfall at these levels: qvar_<estimation>_<level> / qes_<estimation>_<level> "
@@ -74,7 +78,8 @@ def main(argv=None) -> int:
     df = load_returns_csv(a.prices, prices=not a.returns)[a.tickers]
     SharedCacheIndexReturns.returns_cache[(tuple(a.tickers), a.start, a.end)] = df
     weights = np.array(a.weights if a.weights else [1.0 / len(a.tickers)] * len(a.tickers))
-    out, runs, es, exact = {}, {}, {}, {}
+    a.es = a.es or a.contributions
+    out, runs, es, esc, exact = {}, {}, {}, {}, {}
     for est in a.estimation:
         calc = ValueAtRiskCalculationFactory.create_var_calculator(copula_type=a.copula, estimation_type=est)
         kw = {"k": a.k} if est == "msm" else {}
@@ -85,6 +90,10 @@ def main(argv=None) -> int:
         if a.es:
             es[est] = runs[est].calc_es(var=out[est])
             print(f"{est}/{a.copula}: mean ES {np.nanmean(es[est]):.4f}", file=sys.stderr)
+        if a.contributions:
+            esc[est] = runs[est].calc_es_contributions(var=out[est])
+            print(f"{est}/{a.copula}: mean ES contributions " +
+                  ", ".join(f"{t} {m:.4f}" for t, m in zip(a.tickers, np.nanmean(esc[est], axis=0))), file=sys.stderr)
         if a.exact_levels:
             exact[est] = runs[est].calc_quantiles(a.exact_levels)
             for i, lv in enumerate(a.exact_levels):
@@ -99,6 +108,9 @@ def main(argv=None) -> int:
             cols[f"var_{k}"] = v
             if k in es:
                 cols[f"{k}_es"] = es[k]                     # next to its VaR column
+            if k in esc:
+                for c, ticker in enumerate(a.tickers):
+                    cols[f"{k}_esc_{ticker}"] = esc[k][:, c]
             if k in exact:
                 for i, lv in enumerate(a.exact_levels):
                     cols[f"qvar_{k}_{lv:g}"] = exact[k][0][:, i]

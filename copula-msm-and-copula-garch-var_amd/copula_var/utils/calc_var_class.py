@@ -133,6 +133,28 @@ class ValueAtRiskCalcualtion:
         es, self.last_tail_mass = self.plan.expected_shortfall(np.asarray(var, dtype=np.float64), self.ptf_mean)
         return es
 
+    def calc_es_contributions(self, var=None, obj_var=0.05, first_guess=-3, second_guess=(-3.5, -2)):
+        """Per-asset contributions to the Expected Shortfall (T, dim), column c = tickers[c]: the
+        Euler allocation w_c E[x_c | portfolio <= VaR] on the VaR's own nested grid (no reference
+        counterpart).  A row sums to calc_es's value minus ptf_mean (the portfolio mean is not
+        allocated).  var=None solves the VaR first.  The mass found below each VaR is kept in
+        last_tail_mass."""
+        if var is None:
+            var = self.calc_var(obj_var, first_guess, second_guess)
+        contrib, self.last_tail_mass = self.plan.es_contributions(np.asarray(var, dtype=np.float64), self.ptf_mean)
+        return contrib
+
+    def calc_var_contributions(self, var=None, band=0.25, obj_var=0.05, first_guess=-3, second_guess=(-3.5, -2)):
+        """Per-asset contributions to the VaR (T, dim): w_c E[x_c | portfolio = VaR] estimated
+        over the band (VaR - band, VaR] of portfolio levels (DESIGN.md §4 justifies the default
+        band from the grid spacing).  A row sums to the band's mean level, kept in
+        last_band_mean (T,); the band's mass is kept in last_tail_mass."""
+        if var is None:
+            var = self.calc_var(obj_var, first_guess, second_guess)
+        contrib, self.last_band_mean, self.last_tail_mass = self.plan.var_contributions(
+            np.asarray(var, dtype=np.float64), self.ptf_mean, band)
+        return contrib
+
     def calc_quantiles(self, levels=(0.05,)):
         """(var, es), each (T, L): the exact quantile of the nested-grid measure at every level
         (plain bisection, none of calc_var's quirks: where calc_var's result lies above -2 + ptf_mean

@@ -156,6 +156,10 @@ struct cvq_plan {
     // marginal tables are the moments' d_mA / d_mB
     size_t capQuant = 0;
     double* d_qwork = nullptr;
+    // risk contributions (cvq_slab_axis_moments / cvq_es_contributions): per-chunk partial sums
+    // [T][chunks][1 + dim]; the marginal tables are the moments' d_mA / d_mB
+    size_t capAttr = 0;
+    double* d_apart = nullptr;
     unsigned long long* d_stamps = nullptr;   // diagnostic phase stamps (CVQ_STAMPS=1)
     bool count_nodes = false;    // cvq_plan_count_nodes: solves record their node counts (stamps)
     bool nodes_valid = false;    // the last solve recorded them
@@ -865,6 +869,10 @@ int launch_quantiles(const StaticDev& S, long long T, hipStream_t stream, const 
                      double* tA, double* tB, double* work, const double* alpha, int L, int K, double min_var,
                      double max_var, double lower, double ptf_mean, double* var_out, double* es_out, double* m0_out,
                      size_t abi);
+size_t attrib_scratch(int dim, int nrows);                                            // cvq_attrib.hip
+int launch_attrib(const StaticDev& S, long long T, hipStream_t stream, const double* a, const double* pi, double* tA,
+                  double* tB, double* part, const double* bounds, const double* var, double lower, double ptf_mean,
+                  double* out_m0, double* out_x, size_t abi);
 }
 namespace {
 
@@ -1185,6 +1193,24 @@ int run_quantiles(cvq_plan* p, const cvq_solve_args& a, int K, const double* lev
                             a.min_var, a.max_var, a.lower, a.ptf_mean, var, es, m0, kernel_abi_key());
 }
 
+// Axis moments: the moments' table scratch + their own partial sums, then tables -> partial sums
+// -> per-date sums (raw, or the contributions of var).
+int run_attrib(cvq_plan* p, const double* bounds, const double* var, double lower, double ptf_mean, double* out_m0,
+               double* out_x) {
+    CVQ_HIP_CHECK(hipSetDevice(p->device));
+    int rc = ensure_moments(p);
+    if (rc) return rc;
+    const size_t need = (size_t)p->T * attrib_scratch(p->S.dim, p->S.nrows);
+    if (need > p->capAttr) {
+        p->capAttr = 0;
+        if ((rc = dev_alloc(&p->d_apart, need))) return rc;
+        p->capAttr = need;
+    }
+    TimedScope ts(p, TK_MOMENTS);
+    return launch_attrib(p->S, p->T, p->stream, p->in_a, p->in_pi, p->d_mA, p->d_mB, p->d_apart, bounds, var, lower,
+                         ptf_mean, out_m0, out_x, kernel_abi_key());
+}
+
 // Invert a symmetric dim x dim matrix (2 or 3) by cofactors; returns det.
 double invert(const double* R, int d, double* Ri) {
     if (d == 2) {
@@ -1207,7 +1233,7 @@ double invert(const double* R, int d, double* Ri) {
 extern "C" {
 
 const char* cvq_last_error(void) { return g_err.c_str(); }
-int32_t cvq_version(void) { return 10300; }
+int32_t cvq_version(void) { return 10400; }
 
 int32_t cvq_device_count(int32_t* count) {
     CVQ_REQUIRE(count != nullptr, CVQ_ERR_INVALID, "count is NULL");
@@ -1461,7 +1487,7 @@ int32_t cvq_plan_destroy(cvq_plan* p) {
     for (void* b : {(void*)p->d_x, (void*)p->d_F, (void*)p->d_phi, (void*)p->d_uvs, (void*)p->d_cf, (void*)p->d_kmax,
                     (void*)p->d_off, (void*)p->d_a, (void*)p->d_pi, (void*)p->d_tA, (void*)p->d_tB,
                     (void*)p->d_C, (void*)p->d_snap, (void*)p->d_hdr, (void*)p->d_err, (void*)p->d_io, (void*)p->d_stamps,
-                    (void*)p->d_mA, (void*)p->d_mB, (void*)p->d_mpart, (void*)p->d_qwork,
+                    (void*)p->d_mA, (void*)p->d_mB, (void*)p->d_mpart, (void*)p->d_qwork, (void*)p->d_apart,
                     (void*)p->d_cutfix, (void*)p->d_kcut, (void*)p->d_fpair, (void*)p->d_ccount, (void*)p->d_tlist, (void*)p->d_tvs, (void*)p->d_defer, (void*)p->d_vstar, (void*)p->d_bucket, (void*)p->d_sidx, (void*)p->d_svs,
                     (void*)p->d_tree, (void*)p->d_pass,
                     (void*)p->d_pidx, (void*)p->d_pvs})
@@ -1675,6 +1701,45 @@ int32_t cvq_expected_shortfall(cvq_plan* p, const cvq_solve_args* a, const doubl
     if (m0_out)
         CVQ_HIP_CHECK(hipMemcpyAsync(m0_out, p->d_io + T, T * sizeof(double), hipMemcpyDeviceToHost, p->stream));
     CVQ_HIP_CHECK(hipMemcpyAsync(es_out, p->d_io + 2 * T, T * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    CVQ_HIP_CHECK(hipStreamSynchronize(p->stream));
+    return CVQ_OK;
+}
+
+int32_t cvq_slab_axis_moments(cvq_plan* p, const double* bounds, double* m0_out, double* mx_out, int32_t mem) {
+    cvq::DeviceScope device_scope;                 // the caller's current device, restored on return
+    CVQ_REQUIRE(p != nullptr && bounds != nullptr && m0_out != nullptr && mx_out != nullptr, CVQ_ERR_INVALID,
+                "NULL argument");
+    CVQ_REQUIRE(p->T > 0, CVQ_ERR_STATE, "cvq_set_dates must be called first");
+    if (mem == CVQ_MEM_DEVICE) return run_attrib(p, bounds, nullptr, 0.0, 0.0, m0_out, mx_out);
+    const long long T = p->T, d = p->S.dim;
+    int rc = ensure_io(p, (3 + d) * T);
+    if (rc) return rc;
+    CVQ_HIP_CHECK(hipSetDevice(p->device));
+    CVQ_HIP_CHECK(hipMemcpyAsync(p->d_io, bounds, 2 * T * sizeof(double), hipMemcpyHostToDevice, p->stream));
+    if ((rc = run_attrib(p, p->d_io, nullptr, 0.0, 0.0, p->d_io + 2 * T, p->d_io + 3 * T))) return rc;
+    CVQ_HIP_CHECK(hipMemcpyAsync(m0_out, p->d_io + 2 * T, T * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    CVQ_HIP_CHECK(hipMemcpyAsync(mx_out, p->d_io + 3 * T, d * T * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    CVQ_HIP_CHECK(hipStreamSynchronize(p->stream));
+    return CVQ_OK;
+}
+
+int32_t cvq_es_contributions(cvq_plan* p, const cvq_solve_args* a, const double* var, double* contrib_out,
+                             double* m0_out, int32_t mem) {
+    cvq::DeviceScope device_scope;                 // the caller's current device, restored on return
+    CVQ_REQUIRE(p != nullptr && a != nullptr && var != nullptr && contrib_out != nullptr, CVQ_ERR_INVALID,
+                "NULL argument");
+    CVQ_REQUIRE(p->T > 0, CVQ_ERR_STATE, "cvq_set_dates must be called first");
+    if (mem == CVQ_MEM_DEVICE) return run_attrib(p, nullptr, var, a->lower, a->ptf_mean, m0_out, contrib_out);
+    const long long T = p->T, d = p->S.dim;
+    int rc = ensure_io(p, (2 + d) * T);
+    if (rc) return rc;
+    CVQ_HIP_CHECK(hipSetDevice(p->device));
+    CVQ_HIP_CHECK(hipMemcpyAsync(p->d_io, var, T * sizeof(double), hipMemcpyHostToDevice, p->stream));
+    if ((rc = run_attrib(p, nullptr, p->d_io, a->lower, a->ptf_mean, p->d_io + T, p->d_io + 2 * T))) return rc;
+    if (m0_out)
+        CVQ_HIP_CHECK(hipMemcpyAsync(m0_out, p->d_io + T, T * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    CVQ_HIP_CHECK(hipMemcpyAsync(contrib_out, p->d_io + 2 * T, d * T * sizeof(double), hipMemcpyDeviceToHost,
+                                 p->stream));
     CVQ_HIP_CHECK(hipStreamSynchronize(p->stream));
     return CVQ_OK;
 }

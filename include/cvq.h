@@ -117,7 +117,8 @@ int32_t cvq_plan_info(const cvq_plan* plan, int64_t* reach_nodes, int32_t* rows)
 
 /* Per-kernel timing with HIP events recorded on the plan's stream (bench.py's
  * live roofline).  kind: 0 tables, 1 joint-mass/prefix, 2 solve, 3 finalize,
- * 4 slab, 5 tail moments (cvq_slab_moments / cvq_expected_shortfall: their tables,
+ * 4 slab, 5 tail moments (cvq_slab_moments / cvq_expected_shortfall and the axis moments
+ * cvq_slab_axis_moments / cvq_es_contributions: their tables,
  * partial sums and finish together), 6 exact quantiles (cvq_quantiles: its tables, passes
  * and updates together).  cvq_plan_timing(mask) times the kinds whose bit (1 << kind) is
  * set (0 = off, 0x7F = all) and clears previous records. */
@@ -186,6 +187,30 @@ int32_t cvq_slab_moments(cvq_plan* plan, const double* bounds, double* m0_out, d
  * cvq_solve on the plan's stream without a host synchronisation. */
 int32_t cvq_expected_shortfall(cvq_plan* plan, const cvq_solve_args* args, const double* var,
                                double* es_out, double* m0_out, int32_t mem);
+
+/* No reference counterpart.  Per-axis first moments of the slab (bounds[t][0], bounds[t][1]],
+ * cvq_slab_moments' membership and node masses:  m0_out[t] = sum of the member nodes' mass
+ * (cvq_slab_moments' m0 bit for bit), mx_out[t][c] = sum of x[i_c] x mass for grid axis c.
+ * Axis c carries asset c's marginal (input order).  The membership rule weighs axis c with
+ *   wa[dim - 1] = w[0],  wa[c] = w[c + 1] for c < dim - 1     (Q10),
+ * so sum_c wa[c] mx[c] = cvq_slab_moments' m1 to rounding.  Any bounds are valid (no v_cap
+ * limit, on every strategy); a NaN bound gives 0 everywhere.  Fixed-order sums: bit-identical
+ * between runs and independent of the other dates of the batch; the plan's solve state is
+ * untouched.  bounds [T][2], m0_out [T], mx_out [T][dim], all host|device. */
+int32_t cvq_slab_axis_moments(cvq_plan* plan, const double* bounds, double* m0_out, double* mx_out,
+                              int32_t mem);
+
+/* No reference counterpart.  Euler allocation of the Expected Shortfall of a solved VaR vector:
+ * with (m0, mx) the axis moments of (args->lower, var[t] - args->ptf_mean],
+ *   contrib_out[t][c] = wa[c] mx[c] / m0  =  wa[c] E[x_c | portfolio <= VaR],
+ * which sum over c to cvq_expected_shortfall's es_out[t] - args->ptf_mean (ptf_mean is one
+ * scalar of the portfolio and is not allocated).  The whole row is NaN where var[t] is NaN
+ * (Q3) or m0 == 0.  m0_out [T] receives m0 (may be NULL).  Only lower and ptf_mean of args are
+ * read.  var / contrib_out [T][dim] / m0_out host|device; CVQ_MEM_DEVICE chains behind
+ * device-mode cvq_solve / cvq_expected_shortfall on the plan's stream without a host
+ * synchronisation. */
+int32_t cvq_es_contributions(cvq_plan* plan, const cvq_solve_args* args, const double* var,
+                             double* contrib_out, double* m0_out, int32_t mem);
 
 /* No reference counterpart.  Exact quantiles of the nested-grid measure at up to CVQ_MAX_LEVELS
  * levels per date: the true VaR that cvq_solve's reproduced quirk Q1 misses wherever the
