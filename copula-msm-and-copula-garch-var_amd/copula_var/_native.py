@@ -169,10 +169,16 @@ def ptr(a: np.ndarray) -> C.c_void_p:
     return C.c_void_p(a.ctypes.data)
 
 
+SPECIAL_FN = {"tppf": 0, "ndtri": 1, "erf": 2, "tppf6": 3, "log_node": 4, "log_node_fast": 5, "exp_node": 6,
+              "exp_node7": 7, "exp2_node7": 8, "fast_rcp": 9, "root_nu6": 10, "pow_node": 11, "pow_gen": 12,
+              "pow_half_neg": 13, "pow_half_pos": 14, "pow_half_pos_c7": 15, "tppf_bf": 16}
+
+
 def special(fn: str, x, nu: float = 0.0, device: int = 0) -> np.ndarray:
     """Device t.ppf / norm.ppf / erf (known-answer tests); "tppf6": the solve kernels'
-    integer-nu t.ppf (nu = 6)."""
-    code = {"tppf": 0, "ndtri": 1, "erf": 2, "tppf6": 3}[fn]
+    integer-nu t.ppf (nu = 6); the other names: the node arithmetic of csrc/cvq_special.h,
+    `nu` carrying the helper's one parameter (include/cvq.h: the exponent for the powers)."""
+    code = SPECIAL_FN[fn]
     xx = f64(x).ravel()
     out = np.empty_like(xx)
     check(lib().cvq_special(device, code, float(nu), ptr(xx), xx.size, ptr(out), MEM_HOST), f"cvq_special({fn})")

@@ -288,7 +288,14 @@ class QuadraturePlan:
 
     # ------------------------------------------------------------ quadrature
     def compute_integral(self, bounds) -> np.ndarray:
-        """Drop-in for ValueAtRiskCalcualtion.compute_integral(bounds) -> (T,)."""
+        """Drop-in for ValueAtRiskCalcualtion.compute_integral(bounds) -> (T,).
+
+        Accuracy is relative to the slab's own sum |mass| (~1e-12; 4e-11 on SORTED / SWEEP's Gaussian and
+        fitted-nu Student nodes) except on PREFIX, which forms a slab as a difference of two running row
+        sums and so rounds against all mass at or below bounds[t, 1] (2 n 2^-53 of it): a narrow slab far
+        from the mass can be off by percents of its own value there (2e-2 seen on a 4-node slab of a
+        near-singular 3-D Gaussian).  F(v) for the VaR solve is unaffected; use another strategy, or
+        tail_moments, for narrow slabs."""
         b = N.f64(bounds)
         if b.shape != (self.T, 2):
             raise ValueError(f"bounds must have shape ({self.T}, 2)")

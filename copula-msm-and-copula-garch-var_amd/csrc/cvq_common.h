@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cmath>
 #include <string>
 
 #include "../../include/cvq.h"
@@ -38,6 +39,13 @@ struct StaticDev {
     const long long* off;         // [nrows] row offset into a date's prefix block
     long long G;                  // reachable nodes per date (sum kmax)
 };
+
+// Integer code of a half-integer power b^(+-m/2): m when m is an integer in [0, limit], else -1
+// (the general power exp(ex log b)).  The plan's node_m = half_power_code(nu + dim, 128) and
+// uni_m = half_power_code(nu + 1, 16); cvq_special's power KATs take their code from here too.
+inline int half_power_code(double m, double limit) {
+    return (m == std::floor(m) && m <= limit) ? (int)m : -1;
+}
 
 // var_function's inner-axis coordinate g = (v - lev) / w0 (integration_algo.py:20, Q10), exact:
 // a multiplication when 1 / w0 is exact (w0 a power of two, e.g. the 2-asset weights 1/2).

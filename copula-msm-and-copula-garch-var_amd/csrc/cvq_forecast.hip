@@ -1420,11 +1420,33 @@ __global__ void k_ukf_filter(UkfConst C, const double* __restrict__ prm, long lo
 }
 
 // ------------------------------------------------------------------ KAT
-__global__ void k_special(int fn, TConst tk, const double* __restrict__ x, long long n, double* __restrict__ out) {
+// fn: the codes of cvq.h (cvq_special); m / ex: the power helpers' integer code and exponent
+__global__ void k_special(int fn, TConst tk, int m, double ex, const double* __restrict__ x, long long n,
+                          double* __restrict__ out) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const double v = x[i];
-    out[i] = fn == 0 ? stdtrit(tk, v) : fn == 1 ? ndtri(v) : fn == 2 ? erf(v) : stdtrit_tab_int<6>(tk, v);
+    double r;
+    switch (fn) {
+        case 0: r = stdtrit(tk, v); break;
+        case 1: r = ndtri(v); break;
+        case 2: r = erf(v); break;
+        case 3: r = stdtrit_tab_int<6>(tk, v); break;
+        case 4: r = log_node(v); break;
+        case 5: r = log_node_fast(v); break;
+        case 6: r = exp_node(v); break;
+        case 7: r = exp_node7(v); break;
+        case 8: r = exp2_node7(v); break;
+        case 9: r = fast_rcp(v); break;
+        case 10: r = root_nu<6>(v); break;
+        case 11: r = pow_node(v, m, ex); break;
+        case 12: r = pow_gen(v, ex); break;
+        case 13: r = pow_half_neg(v, m, ex); break;
+        case 14: r = pow_half_pos(v, m, ex); break;
+        case 15: r = pow_half_pos_c<7>(v); break;
+        default: r = stdtrit_tab_bf(tk, v); break;
+    }
+    out[i] = r;
 }
 
 // ------------------------------------------------------------ host helpers
@@ -1993,23 +2015,36 @@ int32_t cvq_ukf_filter(int32_t device, const double* params, int64_t B, const do
 
 int32_t cvq_special(int32_t device, int32_t fn, double nu, const double* x, int64_t n, double* out, int32_t mem) {
     CVQ_REQUIRE(x && out && n >= 1, CVQ_ERR_INVALID, "bad argument");
-    CVQ_REQUIRE(fn >= 0 && fn <= 3, CVQ_ERR_INVALID,
-                "fn must be 0 (t.ppf), 1 (norm.ppf), 2 (erf) or 3 (t.ppf, the solve kernels' nu = 6 path)");
+    CVQ_REQUIRE(fn >= 0 && fn <= 16, CVQ_ERR_INVALID,
+                "fn must be 0 (t.ppf), 1 (norm.ppf), 2 (erf), 3 (t.ppf, the solve kernels' nu = 6 path) or "
+                "4..16 (the node arithmetic of cvq_special.h, see cvq.h)");
     CVQ_REQUIRE(fn != 3 || nu == 6.0, CVQ_ERR_INVALID, "fn 3 is the integer path for nu = 6");
+    CVQ_REQUIRE(fn != 10 || nu == 6.0, CVQ_ERR_INVALID, "fn 10 is the integer root for nu = 6");
+    // the power helpers: nu carries the exponent ex, the integer code comes from the plan's own rule
+    int m = -1;
+    if (fn == 11 || fn == 13) {
+        CVQ_REQUIRE(nu <= 0.0, CVQ_ERR_INVALID, "fn 11 and 13 take an exponent <= 0");
+        m = half_power_code(-2.0 * nu, fn == 11 ? 128.0 : 16.0);
+    } else if (fn == 14) {
+        CVQ_REQUIRE(nu >= 0.0, CVQ_ERR_INVALID, "fn 14 takes an exponent >= 0");
+        m = half_power_code(2.0 * nu, 16.0);
+    } else if (fn == 12) {
+        CVQ_REQUIRE(std::isfinite(nu), CVQ_ERR_INVALID, "fn 12 takes a finite exponent");
+    }
     CVQ_DEVICE_SCOPE(device);
     int rc = CVQ_OK;
     TConst tk{};
     DevBuf cf;
-    if (fn == 0 || fn == 3) {
+    if (fn == 0 || fn == 3 || fn == 16) {
         CVQ_REQUIRE(nu > 0, CVQ_ERR_INVALID, "nu must be > 0");
         if ((rc = make_tconst(nu, &tk, &cf.p))) return rc;
-        CVQ_REQUIRE(fn != 3 || tk.q_c != nullptr, CVQ_ERR_UNSUPPORTED, "no direct t.ppf tables for this nu");
+        CVQ_REQUIRE(fn == 0 || tk.q_c != nullptr, CVQ_ERR_UNSUPPORTED, "no direct t.ppf tables for this nu");
     }
     DevBuf xin, dout;
     const double* d_x;
     double* d_out;
     if ((rc = stage_in(x, n, mem, xin, &d_x)) || (rc = stage_out(out, n, mem, dout, &d_out))) return rc;
-    hipLaunchKernelGGL(k_special, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, fn, tk, d_x, n, d_out);
+    hipLaunchKernelGGL(k_special, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, fn, tk, m, nu, d_x, n, d_out);
     return finish_out(out, n, mem, dout);
 }
 

@@ -37,8 +37,12 @@ static TImage build_timage(double nu) {
     k.nu = nu;
     k.a = nu / 2;
     k.ln_nu = std::log(nu);
-    k.lbeta = std::lgamma(nu / 2) + std::lgamma(0.5) - std::lgamma(nu / 2 + 0.5);
-    k.ln_k = std::lgamma((nu + 1) / 2) - std::lgamma(nu / 2) - 0.5 * std::log(nu * M_PI);
+    // differences of log-gammas in long double: in double each lgamma(nu / 2) carries half an ulp of
+    // its own size (2.8e-14 at nu = 126), which stdtrit's complement branch amplifies tenfold at its
+    // branch point -- 1.0e-13 in t.ppf there against 1.4e-14 with these (tests/test_node_kat_gpu.py)
+    const long double nul = nu;
+    k.lbeta = (double)(lgammal(nul / 2) + lgammal(0.5L) - lgammal(nul / 2 + 0.5L));
+    k.ln_k = (double)(lgammal((nul + 1) / 2) - lgammal(nul / 2) - 0.5L * logl(nul * 3.141592653589793238462643383279502884L));
     k.ln_tail = k.ln_k + (nu - 1) / 2 * k.ln_nu;
     k.split = (k.a + 1.0) / (k.a + 2.5);
     k.ln_a = std::log(k.a);
@@ -1348,10 +1352,8 @@ int32_t cvq_plan_create(const cvq_static* s, int32_t device, cvq_plan** out) {
             S.inv_g_uni = 1.0 / S.g_uni;
             S.node_ex = -(nu + d) / 2;
             S.uni_ex = -(nu + 1) / 2;
-            const double mu = nu + 1;
-            S.uni_m = (mu == std::floor(mu) && mu <= 16.0) ? (int)mu : -1;
-            const double m2 = -2.0 * S.node_ex;
-            S.node_m = (m2 == std::floor(m2) && m2 <= 128.0) ? (int)m2 : -1;
+            S.uni_m = half_power_code(nu + 1, 16.0);
+            S.node_m = half_power_code(-2.0 * S.node_ex, 128.0);
             if (int rc2 = make_tconst(nu, &S.tk, &p->d_cf)) { cvq_plan_destroy(p); return rc2; }
         } else {
             S.term1 = 1 / (std::sqrt(std::pow(2 * M_PI, d) * det));                              // gaussian.py:107

@@ -140,7 +140,7 @@ constexpr double kLogFloor = -1.0e4;
 // by exp2_node7's ldexp, and the sum stays far inside its |x| < 1e9 domain
 constexpr double kGumbelDeadL = -1.0e5;
 // the Gaussian node's exp: the records carry the exponent's terms scaled by log2(e), so the node is
-// 2^E' by exp2_node7 (4.0e-11 relative; no ln2 reduction: two FMAs and a multiply fewer than exp_node7,
+// 2^E' by exp2_node7 (4.05e-11 relative; no ln2 reduction: two FMAs and a multiply fewer than exp_node7,
 // four FMAs fewer than the degree-9 exp_node).  CVQ_SORT_EXP2=0: unscaled records and exp_node7.
 #ifndef CVQ_SORT_EXP2
 #define CVQ_SORT_EXP2 1
@@ -153,7 +153,7 @@ __device__ __forceinline__ double exp_gauss(double x) { return CVQ_SORT_EXP2 ? e
 // pow_node_t's overflow guard is dropped (PM > 0: squarings, v_rcp_f64 + one Newton
 // step, ~1e-15 relative).
 // PM == 0 with m < 0 (a fitted, non-integer nu): b^ex = 2^(ex log2(e) log b), log_node_fast then exp2_node7
-// (4.0e-11 relative; no ln2 reduction and no overflow guard: b < ~1e31 here), CVQ_SORT_EXP2=0: pow_node's
+// (4.05e-11 relative; no ln2 reduction and no overflow guard: b < ~1e31 here), CVQ_SORT_EXP2=0: pow_node's
 // log_node / exp_node (1.4e-14)
 template <int PM>
 __device__ __forceinline__ double pow_fast(double b, int m, double ex) {

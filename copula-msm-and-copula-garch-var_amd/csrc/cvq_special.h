@@ -314,7 +314,9 @@ __device__ __forceinline__ double stdtrit_tab_bf(const TConst& k, double p) {
     const bool centre = pp >= k.p_split;
     const double d = 0.5 - pp;
     // tail variable pp^(1/nu) without library calls (log_node / exp_node, ~1e-14; pp = 0 and NaN
-    // are replaced below)
+    // are replaced below).  exp_node's 1.4e-14 in v is nu times that in p: just under p_split the
+    // quantile is off by up to 4e-14 + nu S 1.4e-14, S = p / (|t| pdf(t)) ~ 0.3 (1.1e-13 at nu = 30,
+    // tests/test_node_kat_gpu.py), still far below the 1e-8 the decisions tolerate
     const double v = exp_node(log_node(pp) * k.inv_nu);
     const double q = centre ? quintic(k.q_c, k.n_qc, d * k.inv_qc) : quintic(k.q_v, k.n_qv, v * k.inv_qv);
     double t = centre ? d * q : -1.0 / (v * q);
@@ -410,7 +412,8 @@ __device__ __forceinline__ double exp_node(double x) {
     return __builtin_amdgcn_ldexp(p, (int)k);
 }
 
-// exp(x) as exp_node with a degree-7 polynomial (relative error 4.0e-11 on |r| <= ln2 / 2, fitted
+// exp(x) as exp_node with a degree-7 polynomial (relative error 4.05e-11 on |r| <= ln2 / 2 -- its
+// largest, 4.045e-11, at the interval's ends; tests/test_node_reference_cpu.py recomputes it -- fitted
 // to equioscillate; tools/exp_fit.py), two FMAs shorter -- node noise 2.5 decades under the 1e-8
 // the decisions tolerate and under the 1e-10 the slab (compute_integral) tests hold.  Same domain
 // as exp_node.  The SORTED Gaussian node's exp with CVQ_SORT_EXP2=0 (default: exp2_node7 below).
@@ -431,7 +434,7 @@ __device__ __forceinline__ double exp_node7(double x) {
 
 // 2^x as exp_node7 in t = r / ln2 (coefficient k times ln2^k; tools/exp_fit.py --base2): k = rint(x),
 // t = x - k exact, no ln2 reduction -- for arguments already scaled by log2(e) (the SORTED Gaussian
-// records).  4.0e-11 relative; x < -1075 underflows to 0, NaN stays NaN; finite |x| < 1e9.
+// records).  4.05e-11 relative (4.045e-11 at t = +-1/2); x < -1075 underflows to 0, NaN stays NaN; finite |x| < 1e9.
 __device__ __forceinline__ double exp2_node7(double x) {
     const double k = __builtin_rint(x);
     const double t = x - k;

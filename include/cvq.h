@@ -361,7 +361,27 @@ int32_t cvq_garch_loglik_pq(int32_t device, int32_t p, int32_t q, const double* 
 /* Special functions on the device (known-answer tests against scipy):
  * fn 0 = t.ppf(u, nu) (student.py:102), 1 = norm.ppf (gaussian.py:44),
  * 2 = erf (utils/utils.py:20), 3 = t.ppf as the solve kernels' tables evaluate it for
- * nu = 6 (integer-nu root, nu must be 6). */
+ * nu = 6 (integer-nu root, nu must be 6).
+ *
+ * fn 4..16: the device-only node arithmetic of csrc/cvq_special.h, one code per helper
+ * (known-answer tests against a 50-digit reference, tests/test_node_kat_gpu.py).  `nu`
+ * carries the helper's one parameter:
+ *    4 log_node(x)          5 log_node_fast(x)     6 exp_node(x)       7 exp_node7(x)
+ *    8 exp2_node7(x)        9 fast_rcp(x)         10 root_nu<6>(x)     (nu must be 6)
+ *   11 pow_node(x, m, ex)      nu = ex <= 0, m = the plan's node_m rule on -2 ex (limit 128)
+ *   12 pow_gen(x, ex)          nu = ex
+ *   13 pow_half_neg(x, m, ex)  nu = ex <= 0, m = the plan's uni_m rule on -2 ex (limit 16)
+ *   14 pow_half_pos(x, m, ex)  nu = ex >= 0, m = the same rule on 2 ex
+ *   15 pow_half_pos_c<7>(x)
+ *   16 stdtrit_tab_bf(x)       nu = nu; CVQ_ERR_UNSUPPORTED where the plan builds no direct
+ *                              tables for this nu (as fn 3)
+ * Slab tier only (they live in kernel headers that k_special's translation unit cannot
+ * include without the solve kernels; tests/test_node_slabs_gpu.py holds them through the
+ * slab sums): pow_node_t (cvq_direct_kernels.h: DIRECT and COMPACT slabs, which both run
+ * k_direct), pow_fast incl. SORTED's exp2_node7(ex log2(e) log_node_fast(b)) power, and
+ * exp_gauss (cvq_sorted_kernels.h: SORTED and SWEEP slabs).  Not reached by either tier:
+ * COMPACT's own copy of that fast power (cvq_compact_kernels.h), which runs in its solve
+ * only and is held through the solves' VaR parity alone. */
 int32_t cvq_special(int32_t device, int32_t fn, double nu, const double* x, int64_t n,
                     double* out, int32_t mem);
 
