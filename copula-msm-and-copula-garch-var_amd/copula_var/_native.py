@@ -82,6 +82,8 @@ def _declare(lib: C.CDLL) -> None:
         "cvq_plan_nodes_evaluated": (i32, [v, C.POINTER(i64)]),
         "cvq_set_dates": (i32, [v, i64, v, v, i32]),
         "cvq_set_fast_hint": (i32, [v, i32]),
+        "cvq_plan_set_sorted_threads": (i32, [v, i32]),
+        "cvq_plan_get_sorted_threads": (i32, [v, _ip]),
         "cvq_slab": (i32, [v, v, v, i32]),
         "cvq_slab_moments": (i32, [v, v, v, v, i32]),
         "cvq_expected_shortfall": (i32, [v, C.POINTER(CvqSolveArgs), v, v, v, i32]),

@@ -125,6 +125,7 @@ class QuadraturePlan:
         self._wide: Optional["QuadraturePlan"] = None       # unrestricted sibling (auto, level > v_cap)
         self._dates = None                                  # last set_dates / set_dates_device arguments
         self._stream, self._timing, self._counting = None, False, False   # forwarded to the sibling
+        self._sorted_nt = 0                                 # set_sorted_threads (forwarded too)
         self._last: Optional["QuadraturePlan"] = None       # plan of the last device solve (solve_status)
         self._counted: Optional["QuadraturePlan"] = None    # plan that ran the last solve / slab (node counts)
         if strategy == "auto":
@@ -181,6 +182,7 @@ class QuadraturePlan:
                 (self._wide.set_dates if kind == "host" else self._wide.set_dates_device)(*args)
             self._wide.enable_timing(self._timing)
             self._wide.count_nodes(self._counting)
+            self._wide.set_sorted_threads(self._sorted_nt)
         return self._wide._route(top)
 
     @staticmethod
@@ -239,6 +241,22 @@ class QuadraturePlan:
         self._counting = bool(on)
         if self._wide is not None:
             self._wide.count_nodes(on)
+
+    def set_sorted_threads(self, nt: int) -> None:
+        """Diagnostic: threads per date of the SORTED / SWEEP launches -- 256, 384, 512 or 1024, or 0
+        for the automatic rule (cvq_plan_set_sorted_threads).  Every width gives bit-identical results.
+        ValueError for another value, or a width below what the grid needs (2-D n > 512: 1024)."""
+        N.check(N.lib().cvq_plan_set_sorted_threads(self._h, int(nt)), "cvq_plan_set_sorted_threads")
+        self._sorted_nt = int(nt)
+        if self._wide is not None:
+            self._wide.set_sorted_threads(nt)
+
+    def sorted_threads(self) -> int:
+        """The width the next SORTED / SWEEP launch takes for the current dates: the forced value,
+        else the automatic rule's."""
+        nt = C.c_int32()
+        N.check(N.lib().cvq_plan_get_sorted_threads(self._h, C.byref(nt)), "cvq_plan_get_sorted_threads")
+        return int(nt.value)
 
     def nodes_evaluated(self) -> int:
         """Nodes evaluated by the last counted solve, summed over its dates (read from the

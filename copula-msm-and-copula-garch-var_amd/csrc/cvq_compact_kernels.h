@@ -72,17 +72,12 @@ constexpr int kBucketsPerPoint = 4;                 // grid lookup buckets per g
 // table keeps 6 of the HBM table's 8 columns.
 template <int COP>
 constexpr bool kColgInRow = COP != CVQ_PLACKETT;      // (generic kernel only)
-#ifndef CVQ_COMPACT_WAVES
-#define CVQ_COMPACT_WAVES 0                         // min waves per SIMD (0: compiler default)
-#endif
 #ifndef CVQ_COMPACT_ILP
 #define CVQ_COMPACT_ILP 2
 #endif
 constexpr int kIlp = CVQ_COMPACT_ILP;               // independent node chains per row range
-#ifndef CVQ_COMPACT_EXP2
-#define CVQ_COMPACT_EXP2 1                          // fitted-nu power and Gaussian node by exp2_node7
-#endif
-constexpr double kGaussQ = CVQ_COMPACT_EXP2 ? -0.5 * 1.4426950408889634 : -0.5;   // Gaussian exponent scale
+// the fitted-nu power and the Gaussian node are 2^x by exp2_node7: the Gaussian exponent carries log2(e)
+constexpr double kGaussQ = -0.5 * 1.4426950408889634;
 #ifndef CVQ_COMPACT_ILP0
 #define CVQ_COMPACT_ILP0 1                          // node chains of the general (non-integer nu) power
 #endif
@@ -354,19 +349,16 @@ __device__ __forceinline__ double fast_f(const StaticDev& S, const FastRow& f, d
             const double y2 = y * y;
             return y2 * y2;
         } else {
-#if CVQ_COMPACT_EXP2
             if (PM == 0 && S.node_m < 0) {               // fitted nu: 2^(ex log2(e) log b), 4e-11 (cvq_sorted_kernels.h pow_fast)
                 const double y = exp2_node7((S.node_ex * 1.4426950408889634) * log_node_fast(b));
                 return b < 1.0e300 ? y : (b == b ? 0.0 : b);   // ex < 0: +inf -> 0, NaN stays NaN
             }
-#endif
             return pow_node_t<PM>(b, S.node_m, S.node_ex);
         }
     } else if constexpr (COP == CVQ_GAUSSIAN) {
-        // exp(-qf / 2) = 2^E', E' = -log2(e) qf / 2 from the scaled row records (exp2_node7: 4e-11 relative;
-        // CVQ_COMPACT_EXP2=0: kGaussQ = -1/2 and the library exp)
+        // exp(-qf / 2) = 2^E', E' = -log2(e) qf / 2 from the scaled row records (exp2_node7: 4e-11 relative)
         const double E = fma(zc, fma(zc, kGaussQ * S.Ri[3], f.c1), f.c0);
-        return CVQ_COMPACT_EXP2 ? exp2_node7(E) : exp(E);
+        return exp2_node7(E);
     } else {
         const double a1 = S.theta - 1.0;
         const double num = fma(f.c1, zc, f.c0);
@@ -497,11 +489,6 @@ __device__ __forceinline__ void fused_finalize(const SolveConst& P, Header* hdr,
 // Thread tid owns rows tid + NT k (k < RPT, RPT = ceil(n / NT)); NT = 64 makes the
 // whole solve one wavefront: no barriers, no LDS round trips in the reductions.
 // FUSED: evaluate the date's tables here; else read k_tables' tA / tB.
-#if CVQ_COMPACT_WAVES > 0
-#define CVQ_COMPACT_BOUNDS(NT) __launch_bounds__(NT, CVQ_COMPACT_WAVES)
-#else
-#define CVQ_COMPACT_BOUNDS(NT) __launch_bounds__(NT)
-#endif
 // One date's solve by the whole workgroup: snapshots + this date's header bits.  GEN =
 // false compiles the fast node path only (63 instead of 107 VGPRs at cfg 2: five
 // workgroups per CU instead of four, +8.5%); a date that needs the generic path (pi not
@@ -1086,7 +1073,7 @@ __device__ __forceinline__ bool compact_date(const StaticDev& S, const SolveCons
 // completes the solve: the fast kernel when it deferred nothing, else the generic one.
 // defer[0] = deferred count, defer[1] = the generic kernel's ticket; both reset there.
 template <int COP, bool MSM, int NT, int RPT, int PM, bool FUSED, bool GEN>
-__global__ CVQ_COMPACT_BOUNDS(NT) void k_compact(StaticDev S, SolveConst P, CompactGeom G, const double* __restrict__ a,
+__global__ __launch_bounds__(NT) void k_compact(StaticDev S, SolveConst P, CompactGeom G, const double* __restrict__ a,
                                                 const double* __restrict__ tA, const double* __restrict__ tB,
                                                 const double* __restrict__ pi, double* __restrict__ stamps_out,
                                                 double* __restrict__ snaps, Header* hdr, int* defer, long long T) {

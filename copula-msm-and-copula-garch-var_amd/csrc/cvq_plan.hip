@@ -189,6 +189,7 @@ struct cvq_plan {
     bool kcut_ok = false;
     long long capDefer = 0;
     bool fast_hint = false;      // every date of the batch takes COMPACT's fast path (proven or asserted)
+    int sorted_nt = 0;           // SORTED / SWEEP threads per date (cvq_plan_set_sorted_threads; 0: sorted_threads' rule)
     // SORTED: reachable nodes sorted by v* (device: packed indices + v*; host: v*),
     // ub() of the fixed levels and the bisection trees for the cached solve arguments
     std::vector<double> hvs;
@@ -744,6 +745,7 @@ int ensure_cutfix(cvq_plan* p, const SolveConst& P) {
     // that takes every half-row once gives the same slab, so this is a schedule, not a semantics.
     // Each half-row goes to the kernel as its column range: row | j0 << 10 | len << 20 (len 0: none).
     {
+        CVQ_REQUIRE(n < 1024, CVQ_ERR_UNSUPPORTED, "COMPACT's fixed-slab schedule packs rows, columns and lengths into 10 bits");
         const int NT = compact_nt(), M = NT * ((n + NT - 1) / NT);
         std::vector<int> fp((size_t)3 * M * 2);
         const int cols[3][2] = {{kCutLower, kCutFg}, {kCutSg0, kCutFg}, {kCutFg, kCutSg1}};
@@ -863,7 +865,9 @@ int launch_compact(const StaticDev& S, const SolveConst& P, const CompactGeom& G
 int launch_sorted(const StaticDev& S, const SolveConst& P, const SortedGeom& G, long long T, hipStream_t stream,
                   const double* a, const double* tA, const double* tB, const double* pi, bool fused, int mode,
                   const double* bounds, double* out, double* snaps, Header* hdr, double* stamps,
-                  bool sweep, size_t abi);                                            // cvq_sorted.hip
+                  bool sweep, int forced_nt, size_t abi);                             // cvq_sorted.hip
+int sorted_min_threads(int dim, int n);
+int sorted_threads(long long T, int dim, int n, int cop, int forced);
 int moments_chunk_count(int dim, int nrows);                                          // cvq_moments.hip
 int launch_moments(const StaticDev& S, long long T, hipStream_t stream, const double* a, const double* pi, double* tA,
                    double* tB, double* part, const double* bounds, const double* var, double lower, double ptf_mean,
@@ -905,25 +909,31 @@ SortedGeom sorted_geom(const cvq_plan* p, bool solve) {
     return G;
 }
 
+// Diagnostic phase stamps: CVQ_STAMPS in the environment, or (where the strategy counts nodes)
+// cvq_plan_count_nodes.
+bool want_stamps(const cvq_plan* p, bool counts_nodes = true) {
+    static const bool env_stamps = getenv("CVQ_STAMPS") != nullptr;
+    return env_stamps || (counts_nodes && p->count_nodes);
+}
+
 int launch_solve(cvq_plan* p, const SolveConst& P, double* snaps, Header* hdr) {
     TimedScope ts(p, TK_SOLVE);
     if (sorted_family(p)) {
         int rc = ensure_sorted_tree(p, P);
         if (rc) return rc;
-        static const bool env_stamps = getenv("CVQ_STAMPS") != nullptr;   // diagnostic phase stamps
-        const bool dbg_stamps = env_stamps || p->count_nodes;
+        const bool dbg_stamps = want_stamps(p);
         if (dbg_stamps && (rc = ensure_stamps(p))) return rc;
         p->nodes_valid = p->count_nodes;
         return launch_sorted(p->S, P, sorted_geom(p, true), p->T, p->stream, p->in_a, p->d_tA, p->d_tB, p->in_pi,
                              direct_fused(p), 0, nullptr, nullptr, snaps, hdr,
                              dbg_stamps ? (double*)p->d_stamps : nullptr,
-                             p->strategy == CVQ_STRATEGY_SWEEP && p->pass_ma > 0, kernel_abi_key() ^ (sizeof(SortedGeom) << 40));
+                             p->strategy == CVQ_STRATEGY_SWEEP && p->pass_ma > 0, p->sorted_nt,
+                             kernel_abi_key() ^ (sizeof(SortedGeom) << 40));
     }
     if (p->strategy == CVQ_STRATEGY_COMPACT && p->S.n <= compact_max_n()) {
         int rc = ensure_cutfix(p, P);
         if (rc) return rc;
-        static const bool env_stamps = getenv("CVQ_STAMPS") != nullptr;
-        const bool dbg_stamps = env_stamps || p->count_nodes;
+        const bool dbg_stamps = want_stamps(p);
         double* st = nullptr;
         if (dbg_stamps && (rc = ensure_stamps(p))) return rc;
         if (dbg_stamps) st = (double*)p->d_stamps;
@@ -934,20 +944,16 @@ int launch_solve(cvq_plan* p, const SolveConst& P, double* snaps, Header* hdr) {
             p->capDefer = p->T + 2;
         }
         const bool tab = p->ccount_depth >= 0;
-        // CVQ_FPAIR=0: the fixed slabs' (r, n - 1 - r) half-row pairing instead of the host schedule (A/B)
-        static const bool fpair_sched = !(getenv("CVQ_FPAIR") && atoi(getenv("CVQ_FPAIR")) == 0);
         const CompactGeom G{p->d_cutfix, p->d_vstar, p->d_bucket, p->bx0, p->binv, p->nb,
                             tab ? p->d_ccount : nullptr, p->ccount_depth, p->d_tlist, p->d_tvs,
                             {p->bstart[0], p->bstart[1], p->bstart[2], p->bstart[3]},
-                            (tab && p->kcut_ok) ? p->d_kcut : nullptr, fpair_sched ? p->d_fpair : nullptr};
+                            (tab && p->kcut_ok) ? p->d_kcut : nullptr, p->d_fpair};
         return launch_compact(p->S, P, G, p->T, p->stream, p->in_a, p->d_tA, p->d_tB, p->in_pi, direct_fused(p), st,
                               snaps, hdr, p->d_defer, !p->fast_hint, kernel_abi_key() ^ (sizeof(CompactGeom) << 40));
     }
     if (p->strategy != CVQ_STRATEGY_PREFIX) {
-        // profiling only: CVQ_STAMPS=1 (phase stamps)
-        static const bool dbg_stamps = getenv("CVQ_STAMPS") != nullptr;
         double* st = nullptr;
-        if (dbg_stamps) {
+        if (want_stamps(p, false)) {                       // DIRECT records no node counts
             if (int rc = ensure_stamps(p)) return rc;
             st = (double*)p->d_stamps;
         }
@@ -971,7 +977,7 @@ int launch_slab(cvq_plan* p, const double* bounds, double* out) {
     if (sorted_family(p)) {
         SolveConst P{};
         return launch_sorted(p->S, P, sorted_geom(p, false), p->T, p->stream, p->in_a, p->d_tA, p->d_tB, p->in_pi,
-                             direct_fused(p), 1, bounds, out, nullptr, nullptr, nullptr, false,
+                             direct_fused(p), 1, bounds, out, nullptr, nullptr, nullptr, false, p->sorted_nt,
                              kernel_abi_key() ^ (sizeof(SortedGeom) << 40));
     }
     if (p->strategy != CVQ_STRATEGY_PREFIX) {      // COMPACT: slabs of arbitrary bounds run k_direct
@@ -1237,7 +1243,7 @@ double invert(const double* R, int d, double* Ri) {
 extern "C" {
 
 const char* cvq_last_error(void) { return g_err.c_str(); }
-int32_t cvq_version(void) { return 10400; }
+int32_t cvq_version(void) { return 10500; }
 
 int32_t cvq_device_count(int32_t* count) {
     CVQ_REQUIRE(count != nullptr, CVQ_ERR_INVALID, "count is NULL");
@@ -1601,6 +1607,25 @@ int32_t cvq_plan_nodes_evaluated(cvq_plan* p, int64_t* total) {
 int32_t cvq_set_fast_hint(cvq_plan* p, int32_t on) {
     CVQ_REQUIRE(p != nullptr, CVQ_ERR_INVALID, "plan is NULL");
     p->fast_hint = on != 0;
+    return CVQ_OK;
+}
+
+int32_t cvq_plan_set_sorted_threads(cvq_plan* p, int32_t nt) {
+    CVQ_REQUIRE(p != nullptr, CVQ_ERR_INVALID, "plan is NULL");
+    CVQ_REQUIRE(nt == 0 || nt == 256 || nt == 384 || nt == 512 || nt == 1024, CVQ_ERR_INVALID,
+                "SORTED threads per date: 0 (automatic), 256, 384, 512 or 1024");
+    CVQ_REQUIRE(nt == 0 || nt >= sorted_min_threads(p->S.dim, p->S.n), CVQ_ERR_UNSUPPORTED,
+                "a 2-D grid with n > 512 needs 1024 SORTED threads per date");
+    p->sorted_nt = nt;
+    return CVQ_OK;
+}
+
+int32_t cvq_plan_get_sorted_threads(cvq_plan* p, int32_t* nt) {
+    cvq::DeviceScope device_scope;                 // the rule counts the plan's device's compute units
+    CVQ_REQUIRE(p != nullptr && nt != nullptr, CVQ_ERR_INVALID, "NULL argument");
+    CVQ_REQUIRE(p->T > 0, CVQ_ERR_STATE, "cvq_set_dates must be called first");
+    CVQ_HIP_CHECK(hipSetDevice(p->device));
+    *nt = sorted_threads(p->T, p->S.dim, p->S.n, p->S.copula, p->sorted_nt);
     return CVQ_OK;
 }
 

@@ -2,8 +2,6 @@
 // its template instances compile in parallel with cvq_plan.hip).
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #define CVQ_NO_PLAN_KERNELS
 
 #include "cvq_sorted_launch.h"
@@ -25,6 +23,10 @@ int device_cus() {
 
 }  // namespace
 
+// The narrowest workgroup that holds the grid: a 2-D grid with n > 512 needs the 1024-thread
+// instance (sorted_max_n_nt).
+int sorted_min_threads(int dim, int n) { return n > sorted_max_n_nt(dim, kSortNT) ? 1024 : kSortNT; }
+
 // Threads per date (one workgroup each).  A date is a chain of dependent phases (tables, two
 // fixed slabs, ~10 reduced levels, the tail), so a launch with few dates per CU is latency
 // bound: wider workgroups split every range sum over more lanes and shorten the chain.  The
@@ -33,16 +35,14 @@ int device_cus() {
 // GPU runs 1024- or 512-thread dates, a full batch 256.  Counting whole workgroups per CU instead
 // (625 dates: 384 threads, every workgroup resident) measured slower than 512 threads with the
 // last ~100 dates starting late (cfg 3 133 vs 116 us, cfg 5 118 vs 103 us; profiles/r04o).
-// CVQ_SORT_NT (256 / 384 / 512 / 1024) overrides (A/B).
-// A 2-D grid with n > 512 needs the 1024-thread instance (sorted_max_n_nt).
 // cop: the Gumbel kind's instances are compiled for fewer waves per SIMD (sorted_min_waves), so its
 // residency test counts those; the other kinds keep the width rule's generic value.
-int sorted_threads(long long T, int dim, int n, int cop) {
+// forced: the plan's width (cvq_plan_set_sorted_threads, which admits none below
+// sorted_min_threads); 0: the rule.
+int sorted_threads(long long T, int dim, int n, int cop, int forced) {
+    if (forced) return forced;
     const int wcop = cop == CVQ_GUMBEL ? cop : -1;
-    const int nt_min = n > sorted_max_n_nt(dim, kSortNT) ? 1024 : kSortNT;
-    const char* ev = getenv("CVQ_SORT_NT");            // read per launch: tests switch it per case
-    const int env = ev ? atoi(ev) : 0;
-    if ((env == 256 || env == 384 || env == 512 || env == 1024) && env >= nt_min) return env;
+    const int nt_min = sorted_min_threads(dim, n);
     for (int nt = 1024; nt > nt_min; nt >>= 1)
         if (T * (nt / 64) <= (long long)device_cus() * 4 * sorted_min_waves(dim, nt, wcop)) return nt;
     return nt_min;
@@ -51,7 +51,7 @@ int sorted_threads(long long T, int dim, int n, int cop) {
 int launch_sorted(const StaticDev& S, const SolveConst& P, const SortedGeom& G, long long T, hipStream_t stream,
                   const double* a, const double* tA, const double* tB, const double* pi, bool fused, int mode,
                   const double* bounds, double* out, double* snaps, Header* hdr, double* stamps, bool sweep,
-                  size_t abi) {
+                  int forced_nt, size_t abi) {
     CVQ_REQUIRE(abi == (kernel_abi_key() ^ (sizeof(SortedGeom) << 40)), CVQ_ERR_STATE,
                 "libcvq objects built from different headers (rebuild all)");
     CVQ_REQUIRE(S.copula >= CVQ_GAUSSIAN && S.copula <= CVQ_GUMBEL, CVQ_ERR_INVALID, "unknown copula kind");
@@ -60,7 +60,8 @@ int launch_sorted(const StaticDev& S, const SolveConst& P, const SortedGeom& G, 
     CVQ_REQUIRE(!(sweep && S.n > sorted_max_n_nt(S.dim, kSortNT)), CVQ_ERR_UNSUPPORTED, "SWEEP supports n <= 512");
     const SortedLaunch L{S, P, G, T, stream, a, tA, tB, pi, mode, bounds, out, snaps, hdr, fused, stamps, sweep};
     CVQ_REQUIRE(!(S.copula == CVQ_GUMBEL && !fused), CVQ_ERR_STATE, "the Gumbel kind has fused-table instances only");
-    const int nt = sorted_threads(T, S.dim, S.n, S.copula);
+    const int nt = sorted_threads(T, S.dim, S.n, S.copula, forced_nt);
+    CVQ_REQUIRE(nt >= sorted_min_threads(S.dim, S.n), CVQ_ERR_STATE, "SORTED width below what the grid needs");
     switch (nt) {
         case 1024: sorted_slice_1024(L); break;
         case 512: sorted_slice_512(L); break;

@@ -59,22 +59,10 @@ constexpr int kSortBlk = CVQ_SORT_BLK;
 #ifndef CVQ_SORT_ILP
 #define CVQ_SORT_ILP 4
 #endif
-#ifndef CVQ_SORT_SPLIT
-#define CVQ_SORT_SPLIT 1           // 3-D: r0 split at sg0, the second slab (sg0, fg] from the same reduction
-#endif
-#ifndef CVQ_SORT_SPEC2
-#define CVQ_SORT_SPEC2 1           // 2-D: (fg, sg1] reduced beside r0
-#endif
-#ifndef CVQ_SORT_SKIP
-#define CVQ_SORT_SKIP 1            // range sums skip the partial rounds' slots past the range
-#endif
 // zero words after the node lists: a range sum's prefetch reads up to one round (kSortIlp x the
 // widest workgroup) past its range
 constexpr int kSortIdxPad = CVQ_SORT_ILP * 1024;
 constexpr int kSortIlp = CVQ_SORT_ILP;                // nodes in flight per thread
-#ifndef CVQ_SORT_FLAT2
-#define CVQ_SORT_FLAT2 1           // 2-D table entries spread flat over 1024-thread workgroups too
-#endif
 #ifndef CVQ_SORT_ILP_GEN
 #define CVQ_SORT_ILP_GEN 1
 #endif
@@ -141,24 +129,20 @@ constexpr double kLogFloor = -1.0e4;
 constexpr double kGumbelDeadL = -1.0e5;
 // the Gaussian node's exp: the records carry the exponent's terms scaled by log2(e), so the node is
 // 2^E' by exp2_node7 (4.05e-11 relative; no ln2 reduction: two FMAs and a multiply fewer than exp_node7,
-// four FMAs fewer than the degree-9 exp_node).  CVQ_SORT_EXP2=0: unscaled records and exp_node7.
-#ifndef CVQ_SORT_EXP2
-#define CVQ_SORT_EXP2 1
-#endif
-constexpr double kGaussRecScale = CVQ_SORT_EXP2 ? 1.4426950408889634 : 1.0;   // log2(e)
-__device__ __forceinline__ double exp_gauss(double x) { return CVQ_SORT_EXP2 ? exp2_node7(x) : exp_node7(x); }
+// four FMAs fewer than the degree-9 exp_node).
+constexpr double kGaussRecScale = 1.4426950408889634;   // log2(e)
 
 // b^-(m/2) for the fast path's b = 1 + z^T R^-1 z / nu: the fast path requires finite
 // |z| < 1e15 and R is positive definite, so 1 <= b < ~1e31 and b^(m/2) stays finite:
 // pow_node_t's overflow guard is dropped (PM > 0: squarings, v_rcp_f64 + one Newton
 // step, ~1e-15 relative).
 // PM == 0 with m < 0 (a fitted, non-integer nu): b^ex = 2^(ex log2(e) log b), log_node_fast then exp2_node7
-// (4.05e-11 relative; no ln2 reduction and no overflow guard: b < ~1e31 here), CVQ_SORT_EXP2=0: pow_node's
-// log_node / exp_node (1.4e-14)
+// (4.05e-11 relative; no ln2 reduction and no overflow guard: b < ~1e31 here; pow_node's log_node /
+// exp_node: 1.4e-14)
 template <int PM>
 __device__ __forceinline__ double pow_fast(double b, int m, double ex) {
     if constexpr (PM == 0) {
-        if (CVQ_SORT_EXP2 && m < 0) return exp2_node7((ex * 1.4426950408889634) * log_node_fast(b));
+        if (m < 0) return exp2_node7((ex * 1.4426950408889634) * log_node_fast(b));
         return pow_node(b, m, ex);
     } else {
         constexpr int k = PM >> 1;
@@ -358,10 +342,10 @@ __global__ __launch_bounds__(NT, sorted_min_waves(DIM, NT, COP, PM)) void k_sort
     // index e mod n), so a wide workgroup's table phase is one entry deep (cfg 4 at 1024 threads:
     // 384 of them busy instead of 128; cfg 3's 512-point grid at 1024 threads: one entry per
     // thread instead of both axes on half of them; a lone date's table phase is on its latency
-    // chain).  Otherwise (2-D below 1024 threads, or CVQ_SORT_FLAT2=0) thread tid holds indices
+    // chain).  Otherwise (2-D below 1024 threads) thread tid holds indices
     // tid + NT k of both axes.
     constexpr int RPT = (sorted_max_n_nt(DIM, NT) + NT - 1) / NT;   // grid indices per thread
-    constexpr bool FLAT = DIM == 3 || (CVQ_SORT_FLAT2 && NT >= 1024);   // 2-D at 512 threads: same depth, the division cost 1.5%
+    constexpr bool FLAT = DIM == 3 || NT >= 1024;   // 2-D at 512 threads: same depth, the division cost 1.5%
     constexpr int EPT = FLAT ? (DIM * sorted_max_n_nt(DIM, NT) + NT - 1) / NT : RPT * DIM;   // entries per thread
     constexpr int ILP = sorted_ilp(COP, PM, DIM, NT);              // range sums' nodes in flight
     const int q = MSM ? S.q : 1;
@@ -572,12 +556,12 @@ __global__ __launch_bounds__(NT, sorted_min_waves(DIM, NT, COP, PM)) void k_sort
         const double2 C = rd2(rec2(c));
         if constexpr (COP == CVQ_GAUSSIAN) {
             if constexpr (DIM == 2) {
-                return exp_gauss(fma(A.x, C.x, A.y + C.y));
+                return exp2_node7(fma(A.x, C.x, A.y + C.y));
             } else {
                 const lds_f64* r1 = rec1(c);
                 const double2 Bv = rd2(r1);
                 const double g1 = LAY == kLay3F ? r1[2] : fg1[__builtin_amdgcn_ubfe(c, 9, 8)];
-                return exp_gauss(fma(A.x, fma(g02, C.x, Bv.x), fma(Bv.y, C.x, (A.y + g1) + C.y)));
+                return exp2_node7(fma(A.x, fma(g02, C.x, Bv.x), fma(Bv.y, C.x, (A.y + g1) + C.y)));
             }
         } else if constexpr (COP == CVQ_STUDENT) {
             double b, sc;
@@ -675,7 +659,7 @@ __global__ __launch_bounds__(NT, sorted_min_waves(DIM, NT, COP, PM)) void k_sort
                 const int wb = __builtin_amdgcn_readfirstlane(p);
 #pragma unroll
                 for (int u = 0; u < ILP; ++u) {
-                    if (CVQ_SORT_SKIP && wb + u * NT >= p1) continue;
+                    if (wb + u * NT >= p1) continue;
                     const int q = p + u * NT;
                     const double v = node_fast(c[u]);
                     acc[u] += (q >= p0 && q < p1) ? v : 0.0;
@@ -710,7 +694,7 @@ __global__ __launch_bounds__(NT, sorted_min_waves(DIM, NT, COP, PM)) void k_sort
                 const int wb = __builtin_amdgcn_readfirstlane(p);
 #pragma unroll
                 for (int u = 0; u < ILP; ++u) {
-                    if (CVQ_SORT_SKIP && wb + u * NT >= p1) continue;
+                    if (wb + u * NT >= p1) continue;
                     const double v = node_fast(cn[u]);
                     acc[u] += p + u * NT < p1 ? v : 0.0;
                 }
@@ -943,11 +927,11 @@ __global__ __launch_bounds__(NT, sorted_min_waves(DIM, NT, COP, PM)) void k_sort
         // then comes from the same pass and reduction instead of being evaluated a second time.  Not
         // in 2-D: the BASELINE 2-D workloads' dates have r0 < obj, and the extra live sum costs the
         // Plackett instances an occupancy step (75 -> 81 VGPRs)
-        const bool split = CVQ_SORT_SPLIT && DIM == 3 && G.fix[0] <= G.fix[1] && G.fix[1] <= G.fix[2];
+        const bool split = DIM == 3 && G.fix[0] <= G.fix[1] && G.fix[1] <= G.fix[2];
         // 2-D: the second slab's usual candidate (fg, sg1] (every BASELINE 2-D date has r0 < obj) is
         // summed beside r0 and reduced with it -- one phase and barrier fewer on the date's chain; the
         // same range sums and reduction order as alone, so the values are bit-identical
-        const bool spec2 = CVQ_SORT_SPEC2 && DIM == 2 && G.fix[2] <= G.fix[3];
+        const bool spec2 = DIM == 2 && G.fix[2] <= G.fix[3];
         double r0, n2 = 0.0;
         if (split) {
             const double p2 = range_sum(G.fix[1], G.fix[2]);

@@ -416,7 +416,8 @@ __device__ __forceinline__ double exp_node(double x) {
 // largest, 4.045e-11, at the interval's ends; tests/test_node_reference_cpu.py recomputes it -- fitted
 // to equioscillate; tools/exp_fit.py), two FMAs shorter -- node noise 2.5 decades under the 1e-8
 // the decisions tolerate and under the 1e-10 the slab (compute_integral) tests hold.  Same domain
-// as exp_node.  The SORTED Gaussian node's exp with CVQ_SORT_EXP2=0 (default: exp2_node7 below).
+// as exp_node.  No kernel's node any more (the Gaussian nodes take exp2_node7 below, which is defined
+// in its terms): kept as function 7 of cvq_special.
 __device__ __forceinline__ double exp_node7(double x) {
     const double k = __builtin_rint(x * 1.4426950408889634);
     double r = fma(-k, 6.93147180369123816490e-01, x);

@@ -159,6 +159,18 @@ int32_t cvq_set_dates(cvq_plan* plan, int64_t T, const double* a, const double* 
  * counterpart (a launch-count optimisation of the device-resident path). */
 int32_t cvq_set_fast_hint(cvq_plan* plan, int32_t on);
 
+/* Diagnostic knob: threads per date (one workgroup each) of the SORTED and SWEEP launches.
+ * nt = 0 (the default) leaves the width to the rule -- the widest of 256 / 512 / 1024 whose
+ * waves the device holds at once for the current number of dates; 256, 384, 512 or 1024
+ * forces that instance.  Every width computes bit-identical results.  Any other value:
+ * CVQ_ERR_INVALID.  A non-zero width below what the plan's grid needs (2-D with n > 512
+ * needs 1024): CVQ_ERR_UNSUPPORTED.  Any plan accepts the call; only the SORTED and SWEEP
+ * strategies' solve and slab launches read the setting. */
+int32_t cvq_plan_set_sorted_threads(cvq_plan* plan, int32_t nt);
+/* The width the next SORTED / SWEEP launch takes for the plan's current dates: the forced
+ * value, else the rule's.  CVQ_ERR_STATE before cvq_set_dates. */
+int32_t cvq_plan_get_sorted_threads(cvq_plan* plan, int32_t* nt);
+
 /* Drop-in for ValueAtRiskCalcualtion.compute_integral (calc_var_class.py:179-212)
  * == calc_grids_and_integrals_results (calc_integral.py:8-119):
  * out[t] = integral of the joint copula density over the nested grid of
@@ -378,8 +390,8 @@ int32_t cvq_garch_loglik_pq(int32_t device, int32_t p, int32_t q, const double* 
  * Slab tier only (they live in kernel headers that k_special's translation unit cannot
  * include without the solve kernels; tests/test_node_slabs_gpu.py holds them through the
  * slab sums): pow_node_t (cvq_direct_kernels.h: DIRECT and COMPACT slabs, which both run
- * k_direct), pow_fast incl. SORTED's exp2_node7(ex log2(e) log_node_fast(b)) power, and
- * exp_gauss (cvq_sorted_kernels.h: SORTED and SWEEP slabs).  Not reached by either tier:
+ * k_direct) and pow_fast incl. SORTED's exp2_node7(ex log2(e) log_node_fast(b)) power
+ * (cvq_sorted_kernels.h: SORTED and SWEEP slabs).  Not reached by either tier:
  * COMPACT's own copy of that fast power (cvq_compact_kernels.h), which runs in its solve
  * only and is held through the solves' VaR parity alone. */
 int32_t cvq_special(int32_t device, int32_t fn, double nu, const double* x, int64_t n,

@@ -181,14 +181,15 @@ def test_theta_one_is_the_gaussian_plan_at_rho_zero(case):
 
 # ------------------------------------------------------------------ 5. widths
 @pytest.mark.parametrize("case", ["cfg2_n64", "garch3d_student_n16"])
-def test_widths_bit_identical(case, monkeypatch):
+def test_widths_bit_identical(case):
     z, P, (ref, ref_it, _) = _ref(*BY_CASE[case])
     ptf = float(z["ptf_mean"])
     p = _plan_of(P, "sorted")
     out = {}
     try:
         for w in ("256", "384", "512", "1024"):
-            monkeypatch.setenv("CVQ_SORT_NT", w)
+            p.set_sorted_threads(int(w))
+            assert p.sorted_threads() == int(w)
             out[w] = p.calc_var(ptf)
     finally:
         p.close()

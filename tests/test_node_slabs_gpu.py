@@ -57,11 +57,11 @@ TIERS = {
     # DIRECT and COMPACT slabs both run k_direct (cvq_plan.hip launch_slab: "COMPACT: slabs of arbitrary
     # bounds run k_direct"): pow_node_t, cvq_direct_kernels.h:20-41 and :155 (integer: rcp + one Newton
     # step, ~1e-15; PM == 0: pow_node); Gaussian / Plackett: node_value, cvq_quad_kernels.h:229.
-    # COMPACT's own fast power (cvq_compact_kernels.h:355-363) runs in its solve only, not in a slab.
+    # COMPACT's own fast power (cvq_compact_kernels.h:350-356) runs in its solve only, not in a slab.
     ("direct", "student", False): "precise", ("direct", "student", True): "precise",
     ("direct", "gaussian", False): "precise", ("direct", "plackett", False): "precise",
-    # SORTED and SWEEP slabs: node_fast, cvq_sorted_kernels.h:570-593 -- Gaussian exp_gauss = exp2_node7
-    # (:142-149, 4.0e-11); Student pow_fast (:151-176): fitted nu exp2_node7(ex log2(e) log_node_fast(b)),
+    # SORTED and SWEEP slabs: node_fast, cvq_sorted_kernels.h:554-577 -- Gaussian exp2_node7
+    # (:130-133, 4.0e-11); Student pow_fast (:135-160): fitted nu exp2_node7(ex log2(e) log_node_fast(b)),
     # integer nu squarings + rcp + one Newton step (~1e-15); Plackett: rcp + Newton (:560-565)
     ("sorted", "student", False): "precise", ("sorted", "student", True): "fast",
     ("sorted", "gaussian", False): "fast", ("sorted", "plackett", False): "precise",

@@ -26,9 +26,8 @@ def _need_gpu(gpu_available):
 @pytest.mark.parametrize("width", WIDTHS)
 @pytest.mark.parametrize("case", ["cfg1", "cfg3_n128", "cfg5_n64", "cfg2_n64", "cfg4_k4_n16", "cfg4_k6_n16",
                                   "garch_student_n64", "ukf_plackett_n64", "garch3d_student_n16", "q1_lowvol"])
-def test_width_matches_golden(case, width, monkeypatch):
+def test_width_matches_golden(case, width):
     from copula_var.engine import QuadraturePlan
-    monkeypatch.setenv("CVQ_SORT_NT", width)
     z = load_golden(case)
     msm = str(z["model"]) == "msm"
     vs = z.get("unique_vol_states")
@@ -37,6 +36,8 @@ def test_width_matches_golden(case, width, monkeypatch):
                        z["combos"], z["weights"], z["copula_params"], vol_states=vs, strategy="sorted")
     try:
         p.set_dates(per)
+        p.set_sorted_threads(int(width))
+        assert p.sorted_threads() == int(width)
         var, _ = p.calc_var(float(z["ptf_mean"]))
         b, ref = z["call00_bounds"], z["call00_result"]
         slab = p.compute_integral(b)
@@ -59,7 +60,7 @@ def _workload(cfg_no, T):
 
 
 @pytest.mark.parametrize("cfg,T", [(3, 625), (5, 625), (4, 250)])
-def test_width_full_geometry_identical(cfg, T, monkeypatch):
+def test_width_full_geometry_identical(cfg, T):
     from copula_var.engine import QuadraturePlan
     c, ipt, uvs, ggp, ptf = _workload(cfg, T)
     dens, x, step, combos = ggp
@@ -69,9 +70,11 @@ def test_width_full_geometry_identical(cfg, T, monkeypatch):
     try:
         p.set_dates(ipt)
         for w in WIDTHS:
-            monkeypatch.setenv("CVQ_SORT_NT", w)
+            p.set_sorted_threads(int(w))
+            assert p.sorted_threads() == int(w)
             out[w] = p.calc_var(ptf)
-        monkeypatch.delenv("CVQ_SORT_NT")
+        p.set_sorted_threads(0)
+        assert p.sorted_threads() in (256, 384, 512, 1024)
         out["auto"] = p.calc_var(ptf)
     finally:
         p.close()
@@ -80,4 +83,31 @@ def test_width_full_geometry_identical(cfg, T, monkeypatch):
     for w, (v, it) in out.items():
         assert it == it0, (w, it, it0)
         assert np.array_equal(v, v0), (cfg, w, float(np.max(np.abs(v - v0))))
+
+
+def test_set_sorted_threads_contract():
+    """The setter takes 0 / 256 / 384 / 512 / 1024 only, and no width below what the grid needs
+    (2-D n > 512: the 1024-thread instance, sorted_max_n_nt)."""
+    from copula_var.engine import QuadraturePlan
+    from test_large_grid_gpu import _problem
+    z = load_golden("cfg2_n64")
+    p = QuadraturePlan("msm", "student", 2, z["x_values"], z["step"], z["densities"], z["combos"], z["weights"],
+                       z["copula_params"], vol_states=z["unique_vol_states"], strategy="sorted")
+    try:
+        p.set_dates((z["forecasts_by_states"], z["forecasts"]))
+        with pytest.raises(ValueError):
+            p.set_sorted_threads(300)
+        assert p.sorted_threads() in (256, 384, 512, 1024)       # the rejected value left the rule in place
+    finally:
+        p.close()
+    z, P = _problem(5, 700)
+    p = QuadraturePlan(P.model, P.copula, 2, P.x, P.step, P.dens, P.combos, P.w, z["copula_params"])
+    try:
+        p.set_dates([P.sigma])
+        with pytest.raises(ValueError):
+            p.set_sorted_threads(256)
+        p.set_sorted_threads(1024)
+        assert p.sorted_threads() == 1024
+    finally:
+        p.close()
 

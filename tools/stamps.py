@@ -1,6 +1,6 @@
 """Phase breakdown of the DIRECT / COMPACT solve kernels from s_memtime stamps
 (diagnostic build aid).  Run on the GPU box:
-    python tools/stamps.py [--config 2] [--strategy direct|compact|sorted]"""
+    python tools/stamps.py [--config 2] [--strategy direct|compact|sorted] [--threads N]"""
 import os, sys
 import numpy as np
 sys.path[:0] = [os.path.join(os.path.dirname(__file__), "..", "copula-msm-and-copula-garch-var_amd"),
@@ -22,6 +22,8 @@ dens, x, step, combos = ggp
 p = engine.QuadraturePlan(cfg.model, cfg.copula, cfg.dim, x, step, dens, combos, cfg.weights, cfg.copula_params(),
                           vol_states=uvs, strategy=STRAT)
 p.set_dates(ipt)
+if "--threads" in sys.argv:                    # SORTED / SWEEP threads per date (else the automatic width)
+    p.set_sorted_threads(int(sys.argv[sys.argv.index("--threads") + 1]))
 for _ in range(3):
     var, it = p.calc_var(ptf)
 buf = np.zeros(T * 32, dtype=np.uint64)
