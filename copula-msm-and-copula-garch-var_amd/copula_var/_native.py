@@ -90,6 +90,7 @@ def _declare(lib: C.CDLL) -> None:
         "cvq_slab_axis_moments": (i32, [v, v, v, v, i32]),
         "cvq_es_contributions": (i32, [v, C.POINTER(CvqSolveArgs), v, v, v, i32]),
         "cvq_quantiles": (i32, [v, C.POINTER(CvqSolveArgs), v, i32, v, v, v, i32]),
+        "cvq_conditional_quantiles": (i32, [v, C.POINTER(CvqSolveArgs), i32, v, v, i32, v, v, v, v, i32]),
         "cvq_solve": (i32, [v, C.POINTER(CvqSolveArgs), v, _ip, i32]),
         "cvq_snap_stride": (i32, [C.POINTER(CvqSolveArgs), _ip]),
         "cvq_solve_status": (i32, [v, _ip]),

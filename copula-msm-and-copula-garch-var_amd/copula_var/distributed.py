@@ -62,13 +62,17 @@ class ShardedVaR:
     contrib_local(var_block, contrib_block): optional; per-asset ES contributions of this rank's
     dates from their solved VaR (views [hi - lo] and [hi - lo, dim]), for es_contributions();
     dim: the number of assets (columns of that block).
+    cond_local(block): optional; conditional quantiles of this rank's dates, block [hi - lo, L, 4] =
+    (covar, coes, m0, p_event) per date and level (p_event repeated over the levels), for
+    conditional_quantiles().
     """
 
     def __init__(self, T_total: int, stride: int, local: Callable, finalize: Callable,
                  device: torch.device, group=None, check: Optional[Callable] = None,
                  block_len: Optional[int] = None, hdr_off: Optional[int] = None,
                  es_local: Optional[Callable] = None, quant_local: Optional[Callable] = None,
-                 contrib_local: Optional[Callable] = None, dim: Optional[int] = None):
+                 contrib_local: Optional[Callable] = None, dim: Optional[int] = None,
+                 cond_local: Optional[Callable] = None):
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
@@ -79,6 +83,7 @@ class ShardedVaR:
         self._es_local = es_local
         self._quant_local = quant_local
         self._contrib_local, self.dim = contrib_local, dim
+        self._cond_local = cond_local
         if hdr_off is None:                                   # snapshots, padded to 16 B, then the header
             hdr_off = (self.per * self.stride + 1) & ~1
         self.hdr_off = int(hdr_off)
@@ -140,13 +145,29 @@ class ShardedVaR:
         out = blk if not dist.is_initialized() else _gather(blk, self.world, self.group)
         return out[: self.T_total]
 
+    def conditional_quantiles(self, L: int) -> torch.Tensor:
+        """Conditional quantiles at L levels, [T_total, L, 4] = (covar, coes, m0, p_event) on every
+        rank: each rank fills its own dates into a NaN-padded [per, L, 4] block; one all-gather.
+        Dates are independent, as in quantiles()."""
+        if self._cond_local is None:
+            raise RuntimeError("this ShardedVaR was built without cond_local")
+        blk = torch.full((self.per, int(L), 4), float("nan"), dtype=torch.float64, device=self.var.device)
+        if self.hi > self.lo:
+            self._cond_local(blk[: self.hi - self.lo])
+        out = blk if not dist.is_initialized() else _gather(blk, self.world, self.group)
+        return out[: self.T_total]
 
-def device_sharded_var(plan, args, T_total: int, device: torch.device, group=None, levels=None) -> ShardedVaR:
+
+def device_sharded_var(plan, args, T_total: int, device: torch.device, group=None, levels=None,
+                       conditional=None) -> ShardedVaR:
     """ShardedVaR wired to a QuadraturePlan's device entry points (plan holds this rank's block).
 
     The plan is bound to torch's current stream at every solve, so its kernels, the
     snapshot buffers' initialisation and the collectives are ordered on one stream.
-    levels: the levels quantiles(len(levels)) serves through plan.quantiles_device."""
+    levels: the levels quantiles(len(levels)) serves through plan.quantiles_device.
+    conditional: (axis, cond_tensor) with cond_tensor this rank's dates' event bounds [hi - lo, 2]
+    on `device`; conditional_quantiles(len(levels)) serves them through
+    plan.conditional_quantiles_device at the same levels."""
     stride = plan.snap_stride(args)
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     per = shard(T_total, 0, world)[2]
@@ -173,7 +194,20 @@ def device_sharded_var(plan, args, T_total: int, device: torch.device, group=Non
         plan.quantiles_device(args, levels, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr())
         block.copy_(out.permute(1, 2, 0))
 
+    def cond_local(block):
+        plan.set_stream(torch.cuda.current_stream(device).cuda_stream)
+        axis, cond = conditional
+        cond = cond.to(device=device, dtype=torch.float64).contiguous()
+        Tl, L = block.shape[:2]
+        out = torch.empty((3, Tl, L), dtype=torch.float64, device=device)                      # the ABI's [T][L] arrays
+        pe = torch.empty(Tl, dtype=torch.float64, device=device)
+        plan.conditional_quantiles_device(args, axis, cond.data_ptr(), levels, out[0].data_ptr(), out[1].data_ptr(),
+                                          out[2].data_ptr(), pe.data_ptr())
+        block[..., :3].copy_(out.permute(1, 2, 0))
+        block[..., 3].copy_(pe[:, None].expand(Tl, L))
+
     return ShardedVaR(T_total, stride, local, finalize, device, group, check=plan.solve_status,
                       block_len=block_len, hdr_off=hdr_off, es_local=es_local,
                       quant_local=quant_local if levels is not None else None,
-                      contrib_local=contrib_local, dim=plan.dim)
+                      contrib_local=contrib_local, dim=plan.dim,
+                      cond_local=cond_local if conditional is not None and levels is not None else None)

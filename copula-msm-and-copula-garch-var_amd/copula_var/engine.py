@@ -472,6 +472,42 @@ class QuadraturePlan:
                                       C.c_void_p(es_ptr or 0), C.c_void_p(m0_ptr or 0), N.MEM_DEVICE),
                 "cvq_quantiles")
 
+    # ------------------------------------------------------------ conditional quantiles (CoVaR / CoES)
+    def conditional_quantiles(self, axis: int, cond, levels, ptf_mean: float = 0.0, min_var=-7.5, max_var=0.0,
+                              lower=-100.0, tolerance=1e-6
+                              ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """(covar (T, L), coes (T, L), m0 (T, L), p_event (T,)): quantiles' bisection on the measure
+        restricted to the event cond[t, 0] < x[i_axis] <= cond[t, 1] on grid axis `axis` (asset
+        `axis`, input order; bounds in grid units, +-inf allowed, a NaN bound or an empty interval
+        is the empty event).  p_event is the event's mass over the whole box, the target of level
+        alpha is alpha * p_event; NaN covar / coes where that target lies outside
+        (F_E(min_var), F_E(max_var)] (m0 = F_E(max_var) there), which covers p_event == 0."""
+        lv = N.f64(np.atleast_1d(np.asarray(levels, dtype=np.float64)))
+        if lv.ndim != 1:
+            raise ValueError("levels must be a sequence of numbers")
+        cd = N.f64(cond)
+        if cd.shape != (self.T, 2):
+            raise ValueError(f"cond must have shape ({self.T}, 2)")
+        args = solve_args(ptf_mean, min_var=min_var, max_var=max_var, lower=lower, tolerance=tolerance)
+        out = [np.empty((self.T, lv.size)) for _ in range(3)]
+        pe = np.empty(self.T)
+        N.check(N.lib().cvq_conditional_quantiles(self._h, C.byref(args), int(axis), N.ptr(cd), N.ptr(lv), lv.size,
+                                                  N.ptr(out[0]), N.ptr(out[1]), N.ptr(out[2]), N.ptr(pe),
+                                                  N.MEM_HOST), "cvq_conditional_quantiles")
+        return out[0], out[1], out[2], pe
+
+    def conditional_quantiles_device(self, args: N.CvqSolveArgs, axis: int, cond_ptr: int, levels, covar_ptr: int,
+                                     coes_ptr: Optional[int] = None, m0_ptr: Optional[int] = None,
+                                     pe_ptr: Optional[int] = None) -> None:
+        """conditional_quantiles into device buffers (cond [T][2], covar / coes / m0 [T][L], p_event
+        [T]; args: min_var, max_var, lower, tolerance and ptf_mean are read; levels stay on the
+        host), in stream order: no host synchronisation."""
+        lv = N.f64(np.atleast_1d(np.asarray(levels, dtype=np.float64)))
+        N.check(N.lib().cvq_conditional_quantiles(self._h, C.byref(args), int(axis), C.c_void_p(cond_ptr), N.ptr(lv),
+                                                  lv.size, C.c_void_p(covar_ptr), C.c_void_p(coes_ptr or 0),
+                                                  C.c_void_p(m0_ptr or 0), C.c_void_p(pe_ptr or 0), N.MEM_DEVICE),
+                "cvq_conditional_quantiles")
+
     # ------------------------------------------------------------ device-resident solve
     def solve_device(self, args: N.CvqSolveArgs, var_ptr: int, check: bool = False) -> Optional[int]:
         """calc_var into a device buffer.  check=False: in stream order, no host

@@ -69,6 +69,14 @@ def build_parser() -> argparse.ArgumentParser:
                     help="also compute the exact quantile (true VaR, without calc_var's reproduced quirks) and its "
                          "Expected Shortfall at these levels: qvar_<estimation>_<level> / qes_<estimation>_<level> "
                          "columns in --out")
+    ap.add_argument("--covar", default=None, metavar="TICKER",
+                    help="also compute the portfolio's conditional quantile and Expected Shortfall given that this "
+                         "ticker is at or below its --covar-stress quantile (CoVaR / CoES), and the difference to the "
+                         "quantile given the ticker between its quartiles (Delta-CoVaR), at the levels of "
+                         "--exact-levels (default 0.05): covar_<estimation>_<ticker>_<level>, coes_... and "
+                         "dcovar_... columns in --out")
+    ap.add_argument("--covar-stress", type=float, default=0.05, metavar="Q",
+                    help="the stress event's probability under the ticker's own forecast marginal (default 0.05)")
     return ap
 
 
@@ -79,7 +87,10 @@ def main(argv=None) -> int:
     SharedCacheIndexReturns.returns_cache[(tuple(a.tickers), a.start, a.end)] = df
     weights = np.array(a.weights if a.weights else [1.0 / len(a.tickers)] * len(a.tickers))
     a.es = a.es or a.contributions
-    out, runs, es, esc, exact = {}, {}, {}, {}, {}
+    covar_levels = a.exact_levels or [0.05]
+    if a.covar and a.covar not in a.tickers:
+        raise SystemExit(f"--covar {a.covar}: not one of --tickers")
+    out, runs, es, esc, exact, covar = {}, {}, {}, {}, {}, {}
     for est in a.estimation:
         calc = ValueAtRiskCalculationFactory.create_var_calculator(copula_type=a.copula, estimation_type=est)
         kw = {"k": a.k} if est == "msm" else {}
@@ -99,6 +110,11 @@ def main(argv=None) -> int:
             for i, lv in enumerate(a.exact_levels):
                 print(f"{est}/{a.copula}: mean exact VaR at {lv:g}: {np.nanmean(exact[est][0][:, i]):.4f}",
                       file=sys.stderr)
+        if a.covar:
+            covar[est] = runs[est].calc_covar(a.covar, a.covar_stress, covar_levels)
+            for i, lv in enumerate(covar_levels):
+                print(f"{est}/{a.copula}: mean CoVaR at {lv:g} given {a.covar}: {np.nanmean(covar[est][0][:, i]):.4f}",
+                      file=sys.stderr)
     first = runs[a.estimation[0]]
     portfolio = first.out_sample_data.mean(axis=1).to_numpy()                    # main.py:73
     if a.out:
@@ -115,6 +131,10 @@ def main(argv=None) -> int:
                 for i, lv in enumerate(a.exact_levels):
                     cols[f"qvar_{k}_{lv:g}"] = exact[k][0][:, i]
                     cols[f"qes_{k}_{lv:g}"] = exact[k][1][:, i]
+            if k in covar:
+                for i, lv in enumerate(covar_levels):
+                    for name, arr in zip(("covar", "coes", "dcovar"), covar[k]):
+                        cols[f"{name}_{k}_{a.covar}_{lv:g}"] = arr[:, i]
         frame = pd.DataFrame(cols, index=idx)
         frame["portfolio_return"] = portfolio[:len(frame)]
         frame.to_csv(a.out)

@@ -28,6 +28,7 @@ import time
 
 import numpy as np
 
+from ..conditional import marginal_quantile
 from ..data_loader.load_data import IndexReturnsRetriever
 from ..engine import QuadraturePlan
 
@@ -163,6 +164,40 @@ class ValueAtRiskCalcualtion:
         number.  The masses found below each quantile are kept in last_tail_mass (T, L)."""
         var, es, self.last_tail_mass = self.plan.quantiles(levels, self.ptf_mean)
         return var, es
+
+    def _asset_index(self, asset) -> int:
+        if isinstance(asset, str):
+            tickers = list(self.tickers)
+            if asset not in tickers:
+                raise ValueError(f"{asset!r} is not one of the tickers {tickers}")
+            return tickers.index(asset)
+        asset = int(asset)
+        if not 0 <= asset < self.dim:
+            raise ValueError(f"asset must be in [0, {self.dim}) or a ticker")
+        return asset
+
+    def calc_covar(self, asset, stress=0.05, levels=(0.05,), benchmark=(0.25, 0.75)):
+        """(covar, coes, delta): the portfolio's exact quantile and Expected Shortfall at every
+        level, each (T, L), given that `asset` (an index or a ticker) is in distress -- at or below
+        the `stress` quantile of its own forecast marginal -- and delta = covar under stress minus
+        covar under the benchmark event, the asset between its benchmark[0] and benchmark[1]
+        quantiles (Adrian-Brunnermeier's Delta-CoVaR in Girardi-Ergun's "<=" form; no reference
+        counterpart).  delta is NaN where either covar is; benchmark=None skips the second call
+        and returns delta = None.  The stress call's event mass is kept in last_event_mass (T,)
+        and the masses found below each covar in last_tail_mass (T, L)."""
+        c = self._asset_index(asset)
+        model = self.VaRCalculationMethod.model_kind
+        per, vs = self.integrations_params_t, self.integrations_params_static
+        T = self.plan.T
+        ev = np.column_stack((np.full(T, -np.inf), marginal_quantile(model, per, vs, c, stress)))
+        covar, coes, self.last_tail_mass, self.last_event_mass = self.plan.conditional_quantiles(
+            c, ev, levels, self.ptf_mean)
+        if benchmark is None:
+            return covar, coes, None
+        band = np.column_stack((marginal_quantile(model, per, vs, c, benchmark[0]),
+                                marginal_quantile(model, per, vs, c, benchmark[1])))
+        base = self.plan.conditional_quantiles(c, band, levels, self.ptf_mean)[0]
+        return covar, coes, covar - base
 
     def compute_integral(self, bounds):
         """I_t(a, b] for every date t (calc_var_class.py:179-212), one device launch."""

@@ -164,6 +164,10 @@ struct cvq_plan {
     // [T][chunks][1 + dim]; the marginal tables are the moments' d_mA / d_mB
     size_t capAttr = 0;
     double* d_apart = nullptr;
+    // conditional quantiles (cvq_conditional_quantiles): per-(date, level) partial sums, the p_E
+    // pass's partials, state and cuts; the marginal tables are the moments' d_mA / d_mB
+    size_t capCond = 0;
+    double* d_cwork = nullptr;
     unsigned long long* d_stamps = nullptr;   // diagnostic phase stamps (CVQ_STAMPS=1)
     bool count_nodes = false;    // cvq_plan_count_nodes: solves record their node counts (stamps)
     bool nodes_valid = false;    // the last solve recorded them
@@ -877,6 +881,11 @@ int launch_quantiles(const StaticDev& S, long long T, hipStream_t stream, const 
                      double* tA, double* tB, double* work, const double* alpha, int L, int K, double min_var,
                      double max_var, double lower, double ptf_mean, double* var_out, double* es_out, double* m0_out,
                      size_t abi);
+size_t conditional_scratch(int dim, int nrows);                                       // cvq_conditional.hip
+int launch_conditional(const StaticDev& S, long long T, hipStream_t stream, const double* a, const double* pi,
+                       double* tA, double* tB, double* work, int axis, const double* cond, const double* alpha, int L,
+                       int K, double min_var, double max_var, double lower, double ptf_mean, double* var_out,
+                       double* es_out, double* m0_out, double* pe_out, size_t abi);
 size_t attrib_scratch(int dim, int nrows);                                            // cvq_attrib.hip
 int launch_attrib(const StaticDev& S, long long T, hipStream_t stream, const double* a, const double* pi, double* tA,
                   double* tB, double* part, const double* bounds, const double* var, double lower, double ptf_mean,
@@ -1203,6 +1212,25 @@ int run_quantiles(cvq_plan* p, const cvq_solve_args& a, int K, const double* lev
                             a.min_var, a.max_var, a.lower, a.ptf_mean, var, es, m0, kernel_abi_key());
 }
 
+// Conditional quantiles: the moments' table scratch + a work buffer of their own, then the
+// pass schedule (timed with the exact quantiles, kind 6).
+int run_conditional(cvq_plan* p, const cvq_solve_args& a, int K, int axis, const double* cond, const double* levels,
+                    int L, double* covar, double* coes, double* m0, double* pe) {
+    CVQ_HIP_CHECK(hipSetDevice(p->device));
+    int rc = ensure_moments(p);
+    if (rc) return rc;
+    const size_t need = (size_t)p->T * L * conditional_scratch(p->S.dim, p->S.nrows);
+    if (need > p->capCond) {
+        p->capCond = 0;
+        if ((rc = dev_alloc(&p->d_cwork, need))) return rc;
+        p->capCond = need;
+    }
+    TimedScope ts(p, TK_QUANTILES);
+    return launch_conditional(p->S, p->T, p->stream, p->in_a, p->in_pi, p->d_mA, p->d_mB, p->d_cwork, axis, cond,
+                              levels, L, K, a.min_var, a.max_var, a.lower, a.ptf_mean, covar, coes, m0, pe,
+                              kernel_abi_key());
+}
+
 // Axis moments: the moments' table scratch + their own partial sums, then tables -> partial sums
 // -> per-date sums (raw, or the contributions of var).
 int run_attrib(cvq_plan* p, const double* bounds, const double* var, double lower, double ptf_mean, double* out_m0,
@@ -1243,7 +1271,7 @@ double invert(const double* R, int d, double* Ri) {
 extern "C" {
 
 const char* cvq_last_error(void) { return g_err.c_str(); }
-int32_t cvq_version(void) { return 10500; }
+int32_t cvq_version(void) { return 10600; }
 
 int32_t cvq_device_count(int32_t* count) {
     CVQ_REQUIRE(count != nullptr, CVQ_ERR_INVALID, "count is NULL");
@@ -1498,7 +1526,7 @@ int32_t cvq_plan_destroy(cvq_plan* p) {
                     (void*)p->d_mA, (void*)p->d_mB, (void*)p->d_mpart, (void*)p->d_qwork, (void*)p->d_apart,
                     (void*)p->d_cutfix, (void*)p->d_kcut, (void*)p->d_fpair, (void*)p->d_ccount, (void*)p->d_tlist, (void*)p->d_tvs, (void*)p->d_defer, (void*)p->d_vstar, (void*)p->d_bucket, (void*)p->d_sidx, (void*)p->d_svs,
                     (void*)p->d_tree, (void*)p->d_pass,
-                    (void*)p->d_pidx, (void*)p->d_pvs})
+                    (void*)p->d_pidx, (void*)p->d_pvs, (void*)p->d_cwork})
         if (b) (void)hipFree(b);
     if (p->own_stream) (void)hipStreamDestroy(p->own_stream);
     delete p;
@@ -1801,6 +1829,51 @@ int32_t cvq_quantiles(cvq_plan* p, const cvq_solve_args* a, const double* levels
         CVQ_HIP_CHECK(hipMemcpyAsync(es_out, p->d_io + TL, TL * sizeof(double), hipMemcpyDeviceToHost, p->stream));
     if (m0_out)
         CVQ_HIP_CHECK(hipMemcpyAsync(m0_out, p->d_io + 2 * TL, TL * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    CVQ_HIP_CHECK(hipStreamSynchronize(p->stream));
+    return CVQ_OK;
+}
+
+int32_t cvq_conditional_quantiles(cvq_plan* p, const cvq_solve_args* a, int32_t axis, const double* cond,
+                                  const double* levels, int32_t n_levels, double* covar_out, double* coes_out,
+                                  double* m0_out, double* pe_out, int32_t mem) {
+    cvq::DeviceScope device_scope;                 // the caller's current device, restored on return
+    // arguments first, the plan last: all of it is checked on the host before any device work
+    CVQ_REQUIRE(a != nullptr && cond != nullptr && levels != nullptr && covar_out != nullptr, CVQ_ERR_INVALID,
+                "NULL argument");
+    CVQ_REQUIRE(axis >= 0 && axis < 3, CVQ_ERR_INVALID, "axis must be in [0, dim)");
+    CVQ_REQUIRE(n_levels >= 1 && n_levels <= CVQ_MAX_LEVELS, CVQ_ERR_INVALID, "n_levels must be in [1, CVQ_MAX_LEVELS]");
+    for (int l = 0; l < n_levels; ++l)
+        CVQ_REQUIRE(levels[l] > 0.0 && std::isfinite(levels[l]), CVQ_ERR_INVALID, "a level must be finite and > 0");
+    CVQ_REQUIRE(std::isfinite(a->min_var) && std::isfinite(a->max_var) && a->max_var > a->min_var, CVQ_ERR_INVALID,
+                "max_var must be above min_var");
+    CVQ_REQUIRE(a->tolerance > 0.0 && std::isfinite(a->tolerance), CVQ_ERR_INVALID, "tolerance must be > 0");
+    CVQ_REQUIRE(!(a->lower > a->min_var) && std::isfinite(a->ptf_mean), CVQ_ERR_INVALID,
+                "lower must not be above min_var; ptf_mean must be finite");
+    const double steps = std::ceil(std::log2((a->max_var - a->min_var) / a->tolerance));
+    CVQ_REQUIRE(steps <= (double)kMaxIters, CVQ_ERR_UNSUPPORTED, "bisection needs more than 62 iterations");
+    const int K = steps > 0.0 ? (int)steps : 0;
+    CVQ_REQUIRE(p != nullptr, CVQ_ERR_INVALID, "plan is NULL");
+    CVQ_REQUIRE(axis < p->S.dim, CVQ_ERR_INVALID, "axis must be in [0, dim)");
+    CVQ_REQUIRE(p->T > 0, CVQ_ERR_STATE, "cvq_set_dates must be called first");
+    if (mem == CVQ_MEM_DEVICE)
+        return run_conditional(p, *a, K, axis, cond, levels, n_levels, covar_out, coes_out, m0_out, pe_out);
+    const long long T = p->T, TL = T * n_levels;
+    int rc = ensure_io(p, 3 * TL + 3 * T);
+    if (rc) return rc;
+    CVQ_HIP_CHECK(hipSetDevice(p->device));
+    double* d_cond = p->d_io + 3 * TL;
+    double* d_pe = d_cond + 2 * T;
+    CVQ_HIP_CHECK(hipMemcpyAsync(d_cond, cond, 2 * T * sizeof(double), hipMemcpyHostToDevice, p->stream));
+    double* d_es = (coes_out || m0_out) ? p->d_io + TL : nullptr;     // coes is needed for m0's pass anyway
+    if ((rc = run_conditional(p, *a, K, axis, d_cond, levels, n_levels, p->d_io, d_es,
+                              m0_out ? p->d_io + 2 * TL : nullptr, pe_out ? d_pe : nullptr)))
+        return rc;
+    CVQ_HIP_CHECK(hipMemcpyAsync(covar_out, p->d_io, TL * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    if (coes_out)
+        CVQ_HIP_CHECK(hipMemcpyAsync(coes_out, p->d_io + TL, TL * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    if (m0_out)
+        CVQ_HIP_CHECK(hipMemcpyAsync(m0_out, p->d_io + 2 * TL, TL * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    if (pe_out) CVQ_HIP_CHECK(hipMemcpyAsync(pe_out, d_pe, T * sizeof(double), hipMemcpyDeviceToHost, p->stream));
     CVQ_HIP_CHECK(hipStreamSynchronize(p->stream));
     return CVQ_OK;
 }

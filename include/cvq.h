@@ -249,6 +249,37 @@ int32_t cvq_es_contributions(cvq_plan* plan, const cvq_solve_args* args, const d
 int32_t cvq_quantiles(cvq_plan* plan, const cvq_solve_args* args, const double* levels, int32_t n_levels,
                       double* var_out, double* es_out, double* m0_out, int32_t mem);
 
+/* No reference counterpart.  Conditional quantiles of the nested-grid measure: CoVaR / CoES of
+ * the portfolio given an event on one grid axis (Adrian-Brunnermeier; the "<=" form of
+ * Girardi-Ergun).  Axis c in [0, dim) carries asset c's marginal (input order, as in
+ * cvq_slab_axis_moments).  Per date t the event is a predicate on grid nodes,
+ *   E_t = { node : x[i_axis] > cond[t][0] and x[i_axis] <= cond[t][1] }   (plain FP64 compares;
+ *   +-inf bounds are allowed; a NaN bound or cond[t][1] <= cond[t][0] is the empty event),
+ * and with cvq_quantiles' membership and node masses
+ *   F_E(v) = mass of the nodes of (args->lower, v] that lie in E_t,   p_E[t] = F_E(+inf).
+ * The measure is not normalised and the event sits on grid nodes, so p_E is not the nominal
+ * stress probability: it is returned (pe_out) and it is the normaliser.  Per level
+ * alpha = levels[l] the target is alpha * p_E[t] (one FP64 product), and with
+ * K = ceil(log2((max_var - min_var) / tolerance)):
+ *   not (F_E(min_var) < alpha p_E <= F_E(max_var)):  covar = coes = NaN, m0 = F_E(max_var)
+ *     (this covers p_E == 0);
+ *   else K steps from (lo, hi) = (min_var, max_var): mid = (lo + hi) / 2, lo = mid if
+ *   F_E(mid) < alpha p_E else hi = mid (cvq_quantiles' rule);
+ *   covar = (lo + hi) / 2 + ptf_mean;  m0 = F_E(covar - ptf_mean);
+ *   coes = M1_E / m0 + ptf_mean with M1_E the level-weighted sum over the same nodes (NaN when
+ *   m0 == 0).
+ * Dates are independent (no Q2/Q4 coupling); each date is a fixed-order sum: results are
+ * bit-identical between runs, across batches and across the number of levels asked for.  Runs
+ * on every strategy with no v_cap limit, on scratch of its own: the plan's solve state is
+ * untouched.  Reads only min_var, max_var, lower, tolerance and ptf_mean of args.  levels: host
+ * [n_levels] whatever `mem` says; cond [T][2], covar_out / coes_out / m0_out [T][n_levels] and
+ * pe_out [T] host|device, the last three may be NULL.  CVQ_MEM_DEVICE is stream-ordered without
+ * a host synchronisation.  Timed under kind 6.  CVQ_ERR_INVALID: NULL argument, axis outside
+ * [0, dim), n_levels outside 1..CVQ_MAX_LEVELS, a level <= 0 or NaN, max_var <= min_var. */
+int32_t cvq_conditional_quantiles(cvq_plan* plan, const cvq_solve_args* args, int32_t axis, const double* cond,
+                                  const double* levels, int32_t n_levels, double* covar_out, double* coes_out,
+                                  double* m0_out, double* pe_out, int32_t mem);
+
 /* Drop-in for ValueAtRiskCalcualtion.calc_var (calc_var_class.py:95-177 +
  * bisection_algorithm :250-309), quirks Q1-Q4 reproduced.  var_out [T];
  * iters_out = bisection iterations the reference would run (may be NULL). */
