@@ -29,6 +29,7 @@ MEM_HOST, MEM_DEVICE = 0, 1
 GAUSSIAN, STUDENT, PLACKETT, GUMBEL, GUMBEL_SURVIVAL = 0, 1, 2, 3, 4
 MSM, GARCH, UKF = 0, 1, 2
 STRATEGY_PREFIX, STRATEGY_DIRECT, STRATEGY_COMPACT, STRATEGY_SORTED, STRATEGY_SWEEP = 0, 1, 2, 3, 4
+MAX_PORTFOLIOS = 64                   # CVQ_MAX_PORTFOLIOS: weight vectors per cvq_portfolio_quantiles call
 
 COPULA_KIND = {"gaussian": GAUSSIAN, "student": STUDENT, "plackett": PLACKETT,
                "gumbel": GUMBEL, "gumbel_survival": GUMBEL_SURVIVAL}
@@ -91,6 +92,8 @@ def _declare(lib: C.CDLL) -> None:
         "cvq_es_contributions": (i32, [v, C.POINTER(CvqSolveArgs), v, v, v, i32]),
         "cvq_quantiles": (i32, [v, C.POINTER(CvqSolveArgs), v, i32, v, v, v, i32]),
         "cvq_conditional_quantiles": (i32, [v, C.POINTER(CvqSolveArgs), i32, v, v, i32, v, v, v, v, i32]),
+        "cvq_portfolio_quantiles": (i32, [v, C.POINTER(CvqSolveArgs), v, v, i32, v, i32, v, v, v, i32]),
+        "cvq_portfolio_scratch": (i32, [v, i32, i32, C.POINTER(i64)]),
         "cvq_solve": (i32, [v, C.POINTER(CvqSolveArgs), v, _ip, i32]),
         "cvq_snap_stride": (i32, [C.POINTER(CvqSolveArgs), _ip]),
         "cvq_solve_status": (i32, [v, _ip]),

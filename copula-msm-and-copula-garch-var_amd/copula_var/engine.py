@@ -34,6 +34,8 @@ SORTED_MAX_N = {2: 1024, 3: 255}     # sorted_max_n (cvq_sorted_kernels.h): 2-D 
                                       # 3-D: the 32-bit node word (a0 = i0 + n [i1 == 0] < 2n in 9 bits,
                                       # i1 in 8); its LDS (9 n doubles + a 16-KB tail) is not the bound
 PREFIX_MAX_N_3D = 64                  # PREFIX solves at most 4096 rows (cvq_plan.hip pick_solve_shape)
+PORTFOLIO_SCRATCH_BUDGET = 1 << 30    # bytes of device scratch one cvq_portfolio_quantiles call may take
+                                      # (QuadraturePlan.portfolio_quantiles splits its candidates to stay below)
 MATERIALISED = ("prefix", "sorted", "sweep")   # strategies that hold only nodes with level <= v_cap
 SORTED_ONLY = ("gumbel", "gumbel_survival")     # copulas with SORTED instances only (cvq_plan_create)
 
@@ -507,6 +509,67 @@ class QuadraturePlan:
                                                   lv.size, C.c_void_p(covar_ptr), C.c_void_p(coes_ptr or 0),
                                                   C.c_void_p(m0_ptr or 0), C.c_void_p(pe_ptr or 0), N.MEM_DEVICE),
                 "cvq_conditional_quantiles")
+
+    # ------------------------------------------------------------ quantiles for a batch of weights
+    def _portfolio_inputs(self, weights, ptf_mean, levels):
+        w = N.f64(weights)
+        if w.ndim != 2 or w.shape[1] != self.dim or w.shape[0] < 1:
+            raise ValueError(f"weights must have shape (P, {self.dim}) with P >= 1")
+        pm = N.f64(np.broadcast_to(np.asarray(ptf_mean, dtype=np.float64), (w.shape[0],)))
+        lv = N.f64(np.atleast_1d(np.asarray(levels, dtype=np.float64)))
+        if lv.ndim != 1:
+            raise ValueError("levels must be a sequence of numbers")
+        return w, pm, lv
+
+    def portfolio_scratch(self, n_portfolios: int, n_levels: int) -> int:
+        """Bytes of device scratch one cvq_portfolio_quantiles call of this shape takes."""
+        b = C.c_int64()
+        N.check(N.lib().cvq_portfolio_scratch(self._h, int(n_portfolios), int(n_levels), C.byref(b)),
+                "cvq_portfolio_scratch")
+        return int(b.value)
+
+    def _portfolio_step(self, n_levels: int) -> int:
+        """Candidates per call: at most MAX_PORTFOLIOS, fewer where one call's scratch would pass
+        PORTFOLIO_SCRATCH_BUDGET (at least 1)."""
+        step = N.MAX_PORTFOLIOS
+        if 1 <= n_levels <= 8:                  # an invalid level count is the library's to refuse
+            while step > 1 and self.portfolio_scratch(step, n_levels) > PORTFOLIO_SCRATCH_BUDGET:
+                step = (step + 1) // 2
+        return step
+
+    def portfolio_quantiles(self, weights, levels, ptf_mean=0.0, min_var=-7.5, max_var=0.0, lower=-100.0,
+                            tolerance=1e-6) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(var, es, m0), each (T, P, L): `quantiles` for P candidate weight vectors on this plan's
+        measure.  weights (P, dim) follow the constructor's convention (quirk Q10, see
+        axis_weights; weights[p, 0] > 0, the others may be zero or negative); ptf_mean is a scalar
+        or (P,).  [:, p, :] is bit for bit what `quantiles` returns on a plan built with
+        weights[p] and ptf_mean[p], whatever the other candidates, their number or order.  Any
+        number of candidates: they run in calls of at most MAX_PORTFOLIOS, fewer where a call's
+        scratch would pass PORTFOLIO_SCRATCH_BUDGET; the split does not show in the results."""
+        w, pm, lv = self._portfolio_inputs(weights, ptf_mean, levels)
+        args = solve_args(0.0, min_var=min_var, max_var=max_var, lower=lower, tolerance=tolerance)
+        P = w.shape[0]
+        out = [np.empty((self.T, P, lv.size)) for _ in range(3)]
+        step = self._portfolio_step(lv.size)
+        for p0 in range(0, P, step):
+            wc, pc = N.f64(w[p0:p0 + step]), N.f64(pm[p0:p0 + step])
+            part = [np.empty((self.T, wc.shape[0], lv.size)) for _ in range(3)]
+            N.check(N.lib().cvq_portfolio_quantiles(self._h, C.byref(args), N.ptr(wc), N.ptr(pc), wc.shape[0],
+                                                    N.ptr(lv), lv.size, N.ptr(part[0]), N.ptr(part[1]),
+                                                    N.ptr(part[2]), N.MEM_HOST), "cvq_portfolio_quantiles")
+            for o, q in zip(out, part):
+                o[:, p0:p0 + step, :] = q
+        return out[0], out[1], out[2]
+
+    def portfolio_quantiles_device(self, args: N.CvqSolveArgs, weights, ptf_mean, levels, var_ptr: int,
+                                   es_ptr: Optional[int] = None, m0_ptr: Optional[int] = None) -> None:
+        """portfolio_quantiles of at most MAX_PORTFOLIOS candidates into device buffers [T][P][L]
+        (args: min_var, max_var, lower and tolerance are read; weights, ptf_mean and levels stay on
+        the host), in stream order: no host synchronisation."""
+        w, pm, lv = self._portfolio_inputs(weights, ptf_mean, levels)
+        N.check(N.lib().cvq_portfolio_quantiles(self._h, C.byref(args), N.ptr(w), N.ptr(pm), w.shape[0], N.ptr(lv),
+                                                lv.size, C.c_void_p(var_ptr), C.c_void_p(es_ptr or 0),
+                                                C.c_void_p(m0_ptr or 0), N.MEM_DEVICE), "cvq_portfolio_quantiles")
 
     # ------------------------------------------------------------ device-resident solve
     def solve_device(self, args: N.CvqSolveArgs, var_ptr: int, check: bool = False) -> Optional[int]:

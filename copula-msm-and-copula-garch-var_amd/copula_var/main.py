@@ -20,6 +20,7 @@ import sys
 import numpy as np
 import pandas as pd
 
+from . import portfolios
 from .data_loader.load_data import SharedCacheIndexReturns, load_returns_csv
 from .utils.calc_var_class import ValueAtRiskCalcualtion
 from .utils.factory import ValueAtRiskCalculationFactory
@@ -77,6 +78,12 @@ def build_parser() -> argparse.ArgumentParser:
                          "dcovar_... columns in --out")
     ap.add_argument("--covar-stress", type=float, default=0.05, metavar="Q",
                     help="the stress event's probability under the ticker's own forecast marginal (default 0.05)")
+    ap.add_argument("--weight-grid", type=int, default=None, metavar="STEPS",
+                    help="also compute the exact quantile and Expected Shortfall of every candidate weight vector "
+                         "k / STEPS (non-negative integers summing to STEPS) at the levels of --exact-levels "
+                         "(default 0.05) in one batched device call, and the candidate with the smallest expected "
+                         "loss per date: wbest_<estimation>_<ticker>_<level> (that candidate's weight on the ticker) "
+                         "and wbest_es_<estimation>_<level> columns in --out")
     return ap
 
 
@@ -90,7 +97,9 @@ def main(argv=None) -> int:
     covar_levels = a.exact_levels or [0.05]
     if a.covar and a.covar not in a.tickers:
         raise SystemExit(f"--covar {a.covar}: not one of --tickers")
-    out, runs, es, esc, exact, covar = {}, {}, {}, {}, {}, {}
+    if a.weight_grid is not None and a.weight_grid < 1:
+        raise SystemExit("--weight-grid: STEPS must be >= 1")
+    out, runs, es, esc, exact, covar, wbest = {}, {}, {}, {}, {}, {}, {}
     for est in a.estimation:
         calc = ValueAtRiskCalculationFactory.create_var_calculator(copula_type=a.copula, estimation_type=est)
         kw = {"k": a.k} if est == "msm" else {}
@@ -115,6 +124,19 @@ def main(argv=None) -> int:
             for i, lv in enumerate(covar_levels):
                 print(f"{est}/{a.copula}: mean CoVaR at {lv:g} given {a.covar}: {np.nanmean(covar[est][0][:, i]):.4f}",
                       file=sys.stderr)
+        if a.weight_grid:
+            cand = portfolios.weight_lattice(len(a.tickers), a.weight_grid)
+            p_es = runs[est].calc_portfolio_quantiles(cand, covar_levels)[1]
+            pick, best = portfolios.min_es(p_es)
+            # the candidate's weight per ticker, through the Q10 axis mapping (QuadraturePlan.axis_weights)
+            by_ticker = np.concatenate((cand[:, 1:], cand[:, :1]), axis=1)
+            wbest[est] = (np.where(pick[..., None] >= 0, by_ticker[np.maximum(pick, 0)], np.nan), best)
+            with np.errstate(all="ignore"):
+                mean_es = np.nanmean(p_es, axis=0)
+            for p, wv in enumerate(by_ticker):
+                print(f"{est}/{a.copula}: candidate " + ", ".join(f"{t} {x:g}" for t, x in zip(a.tickers, wv)) +
+                      ": mean ES " + ", ".join(f"{lv:g}: {mean_es[p, i]:.4f}" for i, lv in enumerate(covar_levels)),
+                      file=sys.stderr)
     first = runs[a.estimation[0]]
     portfolio = first.out_sample_data.mean(axis=1).to_numpy()                    # main.py:73
     if a.out:
@@ -135,6 +157,11 @@ def main(argv=None) -> int:
                 for i, lv in enumerate(covar_levels):
                     for name, arr in zip(("covar", "coes", "dcovar"), covar[k]):
                         cols[f"{name}_{k}_{a.covar}_{lv:g}"] = arr[:, i]
+            if k in wbest:
+                for i, lv in enumerate(covar_levels):
+                    for c, ticker in enumerate(a.tickers):
+                        cols[f"wbest_{k}_{ticker}_{lv:g}"] = wbest[k][0][:, i, c]
+                    cols[f"wbest_es_{k}_{lv:g}"] = wbest[k][1][:, i]
         frame = pd.DataFrame(cols, index=idx)
         frame["portfolio_return"] = portfolio[:len(frame)]
         frame.to_csv(a.out)

@@ -165,6 +165,23 @@ class ValueAtRiskCalcualtion:
         var, es, self.last_tail_mass = self.plan.quantiles(levels, self.ptf_mean)
         return var, es
 
+    def calc_portfolio_quantiles(self, weights, levels=(0.05,)):
+        """(var, es), each (T, P, L): calc_quantiles for P candidate weight vectors (P, dim) on this
+        run's fitted measure, all candidates in one device call per 64 (no reference
+        counterpart).  Row p is what calc_quantiles returns from a run constructed with
+        weights=weights[p], its portfolio mean included.  The weights follow the constructor's own
+        convention, quirk Q10: weights[p, k] is NOT ticker k's weight unless the weights are
+        equal -- ticker c carries QuadraturePlan.axis_weights' entry, weights[p, c + 1] for
+        c < dim - 1 and weights[p, 0] for the last ticker; weights[p, 0] must be > 0.  The masses
+        found below each quantile are kept in last_tail_mass (T, P, L)."""
+        w = np.asarray(weights, dtype=np.float64)
+        if w.ndim != 2 or w.shape[1] != self.dim:
+            raise ValueError(f"weights must have shape (P, {self.dim})")
+        means = np.array([self.mean_returns[tk] for tk in self.mean_returns], dtype=np.float64)
+        ptf_mean = np.array([np.sum(means * wp) for wp in w])       # load_data.py:128 per candidate
+        var, es, self.last_tail_mass = self.plan.portfolio_quantiles(w, levels, ptf_mean)
+        return var, es
+
     def _asset_index(self, asset) -> int:
         if isinstance(asset, str):
             tickers = list(self.tickers)

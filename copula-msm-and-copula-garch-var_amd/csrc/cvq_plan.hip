@@ -168,6 +168,10 @@ struct cvq_plan {
     // pass's partials, state and cuts; the marginal tables are the moments' d_mA / d_mB
     size_t capCond = 0;
     double* d_cwork = nullptr;
+    // batched-weights quantiles (cvq_portfolio_quantiles): per-(date, portfolio, level) partial
+    // sums, state and cuts, then the call's weight records; the marginal tables are the moments'
+    size_t capPort = 0;
+    double* d_pwork = nullptr;
     unsigned long long* d_stamps = nullptr;   // diagnostic phase stamps (CVQ_STAMPS=1)
     bool count_nodes = false;    // cvq_plan_count_nodes: solves record their node counts (stamps)
     bool nodes_valid = false;    // the last solve recorded them
@@ -886,6 +890,11 @@ int launch_conditional(const StaticDev& S, long long T, hipStream_t stream, cons
                        double* tA, double* tB, double* work, int axis, const double* cond, const double* alpha, int L,
                        int K, double min_var, double max_var, double lower, double ptf_mean, double* var_out,
                        double* es_out, double* m0_out, double* pe_out, size_t abi);
+size_t portfolio_scratch(int dim, int nrows, long long T, int P, int L);              // cvq_portfolio.hip
+int launch_portfolios(const StaticDev& S, long long T, hipStream_t stream, const double* a, const double* pi,
+                      double* tA, double* tB, double* work, const double* wrec, const double* mean, int P,
+                      const double* alpha, int L, int K, double min_var, double max_var, double lower,
+                      double* var_out, double* es_out, double* m0_out, size_t abi);
 size_t attrib_scratch(int dim, int nrows);                                            // cvq_attrib.hip
 int launch_attrib(const StaticDev& S, long long T, hipStream_t stream, const double* a, const double* pi, double* tA,
                   double* tB, double* part, const double* bounds, const double* var, double lower, double ptf_mean,
@@ -1231,6 +1240,24 @@ int run_conditional(cvq_plan* p, const cvq_solve_args& a, int K, int axis, const
                               kernel_abi_key());
 }
 
+// Batched-weights quantiles: the moments' table scratch + a work buffer of their own, then the
+// pass schedule (timed with the exact quantiles, kind 6).  wrec host [P][4], mean host [P].
+int run_portfolios(cvq_plan* p, const cvq_solve_args& a, int K, const double* wrec, const double* mean, int P,
+                   const double* levels, int L, double* var, double* es, double* m0) {
+    CVQ_HIP_CHECK(hipSetDevice(p->device));
+    int rc = ensure_moments(p);
+    if (rc) return rc;
+    const size_t need = portfolio_scratch(p->S.dim, p->S.nrows, p->T, P, L);
+    if (need > p->capPort) {
+        p->capPort = 0;
+        if ((rc = dev_alloc(&p->d_pwork, need))) return rc;
+        p->capPort = need;
+    }
+    TimedScope ts(p, TK_QUANTILES);
+    return launch_portfolios(p->S, p->T, p->stream, p->in_a, p->in_pi, p->d_mA, p->d_mB, p->d_pwork, wrec, mean, P,
+                             levels, L, K, a.min_var, a.max_var, a.lower, var, es, m0, kernel_abi_key());
+}
+
 // Axis moments: the moments' table scratch + their own partial sums, then tables -> partial sums
 // -> per-date sums (raw, or the contributions of var).
 int run_attrib(cvq_plan* p, const double* bounds, const double* var, double lower, double ptf_mean, double* out_m0,
@@ -1271,7 +1298,7 @@ double invert(const double* R, int d, double* Ri) {
 extern "C" {
 
 const char* cvq_last_error(void) { return g_err.c_str(); }
-int32_t cvq_version(void) { return 10600; }
+int32_t cvq_version(void) { return 10700; }
 
 int32_t cvq_device_count(int32_t* count) {
     CVQ_REQUIRE(count != nullptr, CVQ_ERR_INVALID, "count is NULL");
@@ -1526,7 +1553,7 @@ int32_t cvq_plan_destroy(cvq_plan* p) {
                     (void*)p->d_mA, (void*)p->d_mB, (void*)p->d_mpart, (void*)p->d_qwork, (void*)p->d_apart,
                     (void*)p->d_cutfix, (void*)p->d_kcut, (void*)p->d_fpair, (void*)p->d_ccount, (void*)p->d_tlist, (void*)p->d_tvs, (void*)p->d_defer, (void*)p->d_vstar, (void*)p->d_bucket, (void*)p->d_sidx, (void*)p->d_svs,
                     (void*)p->d_tree, (void*)p->d_pass,
-                    (void*)p->d_pidx, (void*)p->d_pvs, (void*)p->d_cwork})
+                    (void*)p->d_pidx, (void*)p->d_pvs, (void*)p->d_cwork, (void*)p->d_pwork})
         if (b) (void)hipFree(b);
     if (p->own_stream) (void)hipStreamDestroy(p->own_stream);
     delete p;
@@ -1875,6 +1902,74 @@ int32_t cvq_conditional_quantiles(cvq_plan* p, const cvq_solve_args* a, int32_t 
         CVQ_HIP_CHECK(hipMemcpyAsync(m0_out, p->d_io + 2 * TL, TL * sizeof(double), hipMemcpyDeviceToHost, p->stream));
     if (pe_out) CVQ_HIP_CHECK(hipMemcpyAsync(pe_out, d_pe, T * sizeof(double), hipMemcpyDeviceToHost, p->stream));
     CVQ_HIP_CHECK(hipStreamSynchronize(p->stream));
+    return CVQ_OK;
+}
+
+int32_t cvq_portfolio_quantiles(cvq_plan* p, const cvq_solve_args* a, const double* weights, const double* ptf_mean,
+                                int32_t n_portfolios, const double* levels, int32_t n_levels, double* var_out,
+                                double* es_out, double* m0_out, int32_t mem) {
+    cvq::DeviceScope device_scope;                 // the caller's current device, restored on return
+    // arguments first, the plan last: all of it is checked on the host before any device work
+    CVQ_REQUIRE(a != nullptr && weights != nullptr && ptf_mean != nullptr && levels != nullptr && var_out != nullptr,
+                CVQ_ERR_INVALID, "NULL argument");
+    CVQ_REQUIRE(n_portfolios >= 1 && n_portfolios <= CVQ_MAX_PORTFOLIOS, CVQ_ERR_INVALID,
+                "n_portfolios must be in [1, CVQ_MAX_PORTFOLIOS]");
+    CVQ_REQUIRE(n_levels >= 1 && n_levels <= CVQ_MAX_LEVELS, CVQ_ERR_INVALID, "n_levels must be in [1, CVQ_MAX_LEVELS]");
+    for (int l = 0; l < n_levels; ++l)
+        CVQ_REQUIRE(levels[l] > 0.0 && std::isfinite(levels[l]), CVQ_ERR_INVALID, "a level must be finite and > 0");
+    CVQ_REQUIRE(std::isfinite(a->min_var) && std::isfinite(a->max_var) && a->max_var > a->min_var, CVQ_ERR_INVALID,
+                "max_var must be above min_var");
+    CVQ_REQUIRE(a->tolerance > 0.0 && std::isfinite(a->tolerance), CVQ_ERR_INVALID, "tolerance must be > 0");
+    CVQ_REQUIRE(!(a->lower > a->min_var), CVQ_ERR_INVALID, "lower must not be above min_var");
+    for (int q = 0; q < n_portfolios; ++q)
+        CVQ_REQUIRE(std::isfinite(ptf_mean[q]), CVQ_ERR_INVALID, "ptf_mean must be finite");
+    const double steps = std::ceil(std::log2((a->max_var - a->min_var) / a->tolerance));
+    CVQ_REQUIRE(steps <= (double)kMaxIters, CVQ_ERR_UNSUPPORTED, "bisection needs more than 62 iterations");
+    const int K = steps > 0.0 ? (int)steps : 0;
+    CVQ_REQUIRE(p != nullptr, CVQ_ERR_INVALID, "plan is NULL");
+    // the weight records, formed as cvq_plan_create forms the plan's own
+    const int d = p->S.dim, P = n_portfolios;
+    double wrec[CVQ_MAX_PORTFOLIOS][4];
+    for (int q = 0; q < P; ++q) {
+        const double* w = weights + (size_t)q * d;
+        for (int i = 0; i < d; ++i) CVQ_REQUIRE(std::isfinite(w[i]), CVQ_ERR_INVALID, "a weight must be finite");
+    }
+    for (int q = 0; q < P; ++q) {
+        const double* w = weights + (size_t)q * d;
+        CVQ_REQUIRE(w[0] > 0.0, CVQ_ERR_UNSUPPORTED, "weights[p][0] must be > 0 (the inner-axis division, Q10)");
+        int e2 = 0;                                // exact reciprocal: w0 = 2^e and 1/w0 a normal double
+        const double m2 = std::frexp(w[0], &e2);
+        wrec[q][0] = w[0];
+        wrec[q][1] = w[1];
+        wrec[q][2] = d == 3 ? w[2] : 0.0;
+        wrec[q][3] = (m2 == 0.5 && std::isnormal(1.0 / w[0])) ? 1.0 / w[0] : 0.0;
+    }
+    CVQ_REQUIRE(p->T > 0, CVQ_ERR_STATE, "cvq_set_dates must be called first");
+    if (mem == CVQ_MEM_DEVICE)
+        return run_portfolios(p, *a, K, &wrec[0][0], ptf_mean, P, levels, n_levels, var_out, es_out, m0_out);
+    const long long N = p->T * P * n_levels;
+    int rc = ensure_io(p, 3 * N);
+    if (rc) return rc;
+    CVQ_HIP_CHECK(hipSetDevice(p->device));
+    double* d_es = (es_out || m0_out) ? p->d_io + N : nullptr;        // es is needed for m0's pass anyway
+    if ((rc = run_portfolios(p, *a, K, &wrec[0][0], ptf_mean, P, levels, n_levels, p->d_io, d_es,
+                             m0_out ? p->d_io + 2 * N : nullptr)))
+        return rc;
+    CVQ_HIP_CHECK(hipMemcpyAsync(var_out, p->d_io, N * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    if (es_out)
+        CVQ_HIP_CHECK(hipMemcpyAsync(es_out, p->d_io + N, N * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    if (m0_out)
+        CVQ_HIP_CHECK(hipMemcpyAsync(m0_out, p->d_io + 2 * N, N * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    CVQ_HIP_CHECK(hipStreamSynchronize(p->stream));
+    return CVQ_OK;
+}
+
+int32_t cvq_portfolio_scratch(const cvq_plan* p, int32_t n_portfolios, int32_t n_levels, int64_t* bytes) {
+    CVQ_REQUIRE(p != nullptr && bytes != nullptr, CVQ_ERR_INVALID, "NULL argument");
+    CVQ_REQUIRE(n_portfolios >= 1 && n_portfolios <= CVQ_MAX_PORTFOLIOS && n_levels >= 1 && n_levels <= CVQ_MAX_LEVELS,
+                CVQ_ERR_INVALID, "n_portfolios must be in [1, CVQ_MAX_PORTFOLIOS], n_levels in [1, CVQ_MAX_LEVELS]");
+    CVQ_REQUIRE(p->T > 0, CVQ_ERR_STATE, "cvq_set_dates must be called first");
+    *bytes = (int64_t)(portfolio_scratch(p->S.dim, p->S.nrows, p->T, n_portfolios, n_levels) * sizeof(double));
     return CVQ_OK;
 }
 

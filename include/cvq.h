@@ -280,6 +280,38 @@ int32_t cvq_conditional_quantiles(cvq_plan* plan, const cvq_solve_args* args, in
                                   const double* levels, int32_t n_levels, double* covar_out, double* coes_out,
                                   double* m0_out, double* pe_out, int32_t mem);
 
+/* No reference counterpart.  cvq_quantiles for a batch of portfolio weights on one plan: the
+ * exact quantile, Expected Shortfall and mass of the same nested-grid measure for
+ * n_portfolios weight vectors x n_levels levels per date.  Nothing of the measure depends on the
+ * weights (only the membership of a node and its level do), so the marginal tables are built once
+ * per call and one launch sequence serves every portfolio.  For portfolio p,
+ *   var / es / m0 [t][p][:] is what cvq_quantiles returns on a plan that differs only in
+ *   cvq_static.weights = weights[p] and args->ptf_mean = ptf_mean[p],
+ * bit for bit, cvq_plan_create's reciprocal rule included (weights[p][0] a power of two with a
+ * normal reciprocal: multiply by it; else divide).  weights follow cvq_static.weights' convention
+ * (Q10: weights[p][0] scales the inner, last-integrated axis); weights[p][0] <= 0 is
+ * CVQ_ERR_UNSUPPORTED as in cvq_plan_create, the other weights may be zero or negative.
+ * A portfolio's result does not depend on the other portfolios of the call, their number or order,
+ * the number of levels or the other dates, and is bit-identical between runs (fixed-order sums;
+ * no atomics).  K, the bracket rule, the NaN convention outside the bracket and everything else
+ * are cvq_quantiles': runs on every strategy with no v_cap limit, on lazily sized scratch of its
+ * own (cvq_portfolio_scratch; a failed allocation is CVQ_ERR_OOM); the plan's solve state is
+ * untouched.  Reads only min_var, max_var, lower and tolerance of args (args->ptf_mean is not
+ * read).  weights host [n_portfolios][dim], ptf_mean host [n_portfolios], levels host [n_levels]
+ * whatever `mem` says; var_out / es_out / m0_out [T][n_portfolios][n_levels] host|device, the
+ * last two may be NULL.  CVQ_MEM_DEVICE is stream-ordered without a host synchronisation.  Timed
+ * under kind 6.  CVQ_ERR_INVALID (before any device work): NULL argument, n_portfolios outside
+ * 1..CVQ_MAX_PORTFOLIOS, n_levels outside 1..CVQ_MAX_LEVELS, a level <= 0 or NaN,
+ * max_var <= min_var, a non-finite weight or ptf_mean.  K > 62: CVQ_ERR_UNSUPPORTED. */
+#define CVQ_MAX_PORTFOLIOS 64
+int32_t cvq_portfolio_quantiles(cvq_plan* plan, const cvq_solve_args* args, const double* weights,
+                                const double* ptf_mean, int32_t n_portfolios, const double* levels,
+                                int32_t n_levels, double* var_out, double* es_out, double* m0_out, int32_t mem);
+
+/* Bytes of device scratch one cvq_portfolio_quantiles call of this shape takes on the plan's
+ * current batch (a caller splitting a long candidate list sizes its calls with it). */
+int32_t cvq_portfolio_scratch(const cvq_plan* plan, int32_t n_portfolios, int32_t n_levels, int64_t* bytes);
+
 /* Drop-in for ValueAtRiskCalcualtion.calc_var (calc_var_class.py:95-177 +
  * bisection_algorithm :250-309), quirks Q1-Q4 reproduced.  var_out [T];
  * iters_out = bisection iterations the reference would run (may be NULL). */
