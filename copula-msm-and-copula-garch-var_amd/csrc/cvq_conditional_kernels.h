@@ -124,18 +124,54 @@ __global__ __launch_bounds__(kMomNT) void k_cond_pass(StaticDev S, const double*
     }
     jlo = __builtin_amdgcn_readfirstlane(jlo);
     jhi = __builtin_amdgcn_readfirstlane(jhi);
-    // this wave's share of the chunk's range
-    int j0 = jlo, j1 = jhi;
-    if (CS > 1 && jhi >= jlo) {
-        const int per = (jhi - jlo + CS) / CS;
-        j0 = jlo + (wave % CS) * per;
-        j1 = min(jhi, j0 + per - 1);
+    // This wave's share of the chunk's range.  The split opening pass (2-D) takes k_quant_pass' own
+    // range first -- the union over the cuts below +inf, [jlo9, jhi9], split among the waves as there --
+    // and then the columns only the +inf cut reaches, below and above it, split the same way: a cut
+    // below +inf then sums the columns k_quant_pass sums, per wave and in its order, so the event
+    // (-inf, +inf) gives cvq_quantiles' F bit for bit, as the unsplit 3-D pass does by itself.
+    constexpr bool SPLIT3 = CS > 1 && !SKEW;
+    constexpr int NSEG = SPLIT3 ? 3 : 1;
+    int seg_lo[NSEG], seg_hi[NSEG];
+    seg_lo[0] = jlo;
+    seg_hi[0] = jhi;
+    if constexpr (SPLIT3) {
+        int kb9 = 0;
+#pragma unroll
+        for (int i = 0; i < C - 1; ++i) kb9 = max(kb9, kb[i]);
+        int jlo9 = kb9 > ka ? ka + 1 : n, jhi9 = kb9 > ka ? kb9 : -1;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            jlo9 = min(jlo9, __shfl_xor(jlo9, o, 64));
+            jhi9 = max(jhi9, __shfl_xor(jhi9, o, 64));
+        }
+        jlo9 = __builtin_amdgcn_readfirstlane(jlo9);
+        jhi9 = __builtin_amdgcn_readfirstlane(jhi9);
+        if (jhi9 >= jlo9) {                       // (then jlo <= jlo9 and jhi9 <= jhi: kbmax >= kb9 on every lane)
+            seg_lo[0] = jlo9;  seg_hi[0] = jhi9;
+            seg_lo[1] = jlo;   seg_hi[1] = jlo9 - 1;
+            seg_lo[2] = jhi9 + 1;  seg_hi[2] = jhi;
+        } else {
+            seg_lo[1] = seg_lo[2] = n;
+            seg_hi[1] = seg_hi[2] = -1;
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < NSEG; ++g) {
+        if (CS > 1 && seg_hi[g] >= seg_lo[g]) {
+            const int per = (seg_hi[g] - seg_lo[g] + CS) / CS;
+            const int lo = seg_lo[g] + (wave % CS) * per;
+            seg_hi[g] = min(seg_hi[g], lo + per - 1);
+            seg_lo[g] = lo;
+        }
     }
 
     double m0[C], m1[C];
 #pragma unroll
     for (int i = 0; i < C; ++i) m0[i] = m1[i] = 0.0;
-    if (j1 >= j0) {
+    bool any = false;
+#pragma unroll
+    for (int g = 0; g < NSEG; ++g) any = any || seg_hi[g] >= seg_lo[g];
+    if (any) {
         // ---- row weights G[b] (outer axes contracted with pi_t), as k_moments
         double G[QT];
         if (DIM == 2) {
@@ -169,7 +205,10 @@ __global__ __launch_bounds__(kMomNT) void k_cond_pass(StaticDev S, const double*
         RowCtx ctx;
         if (DIM == 2) ctx = make_row<COP, DIM>(S, At[i0], 0.0, Bt[i0]);
         else ctx = make_row<COP, DIM>(S, At[i0], At[n + i1], outer_B<COP>(Bt[i0], Bt[n + i1]));   // prod over axes in order
-        for (int k = j0; k <= j1; ++k) {          // wave-uniform trip count
+        for (int g = 0; g < NSEG; ++g) {
+        const int kl = g == 0 ? seg_lo[0] : g == 1 ? seg_lo[NSEG > 1 ? 1 : 0] : seg_lo[NSEG > 2 ? 2 : 0];
+        const int kh = g == 0 ? seg_hi[0] : g == 1 ? seg_hi[NSEG > 1 ? 1 : 0] : seg_hi[NSEG > 2 ? 2 : 0];
+        for (int k = kl; k <= kh; ++k) {          // wave-uniform trip count
             const int jm = SKEW ? ka + 1 + k : k;               // the column whose membership is tested
             const int j = SKEW ? min(jm, n - 1) : k;            // the column loaded (in the grid)
             double W = 0.0;
@@ -186,6 +225,7 @@ __global__ __launch_bounds__(kMomNT) void k_cond_pass(StaticDev S, const double*
                     }
                 }
             }
+        }
         }
     }
 #pragma unroll

@@ -258,3 +258,153 @@ def problem_inputs(case, z):
     return dict(model=model, copula=copula, dim=dim, x_values=x, step=step, densities=np.ones((dim, 1, n)),
                 combos=np.zeros((1, dim)), weights=w, copula_params=cp,
                 per_date=sigma_rows(copula, dim, params), unique_vol_states=None)
+
+
+# ------------------------------------------------------------------ extension: Gumbel kinds, chunk edges, events, candidates
+# A second fixture (tests/kat/gen_node_kat_ext.py writes it) holds the truths of the cases below and, for
+# them and for every case of cases(), the truths of the conditional and batched-weight passes.  It is kept
+# apart from node_kat.kat, whose bytes and case indices do not move.
+EXT_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "node_kat_ext.kat")
+EXT_GEN_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "kat", "gen_node_kat_ext.py")
+GUMBEL_KINDS = ("gumbel", "gumbel_survival")
+# 1: c == 1; 1 + 2^-30: the cancellation in theta - 1; 16: the plan's cap
+GUMBEL_THETA = (1.0, 1.0 + 2.0 ** -30, 1.5, 4.0, 16.0)
+# chunk edges of the row cores: 2-D n = 70 is two 64-row chunks, 6 live rows in the second; 3-D n = 17 is
+# 289 rows, one 256-row chunk plus 33
+N_EDGE = {2: 70, 3: 17}
+NR1_FACTOR = 1.0 + 2.0 ** -20             # one entry of pi_t scaled by it, then renormalised: pi_t is not rank 1
+
+
+EXP7_BAR = 4.05e-11                       # exp2_node7's own polynomial error (tests/test_node_reference_cpu.py)
+
+
+def gumbel_bar(ebound, tier):
+    """The bar of a Gumbel slab sum, as a share of its sum |mass|: 1e-12 plus the device formulas' first-order
+    bound (tests/gumbel_node_reference.py; the fixture's ebound, or ebound_fast on SORTED's record path, whose
+    outer exp2_node7 adds its own error)."""
+    return 1e-12 + np.asarray(ebound, dtype=np.float64) + (EXP7_BAR if tier == "fast" else 0.0)
+
+
+def load_ext():
+    return dict(np.load(EXT_PATH, allow_pickle=False))
+
+
+def ext_cases():
+    """[(model, copula, dim, params, n, variant)]: a case's index is its row in the extension
+    fixture's slab truths.  variant "nr1": MSM dates whose pi_t is not rank 1 (SORTED then runs
+    node_value, the generic path)."""
+    out = []
+    for m in ("garch", "msm"):
+        for kind in GUMBEL_KINDS:
+            for dim in (2, 3):
+                out += [(m, kind, dim, (th,), N_OF[dim], "") for th in GUMBEL_THETA]
+    for kind in GUMBEL_KINDS:
+        out += [("msm", kind, dim, (4.0,), N_OF[dim], "nr1") for dim in (2, 3)]
+    for m in ("garch", "msm"):
+        for kind in GUMBEL_KINDS:
+            out += [(m, kind, dim, (4.0,), N_EDGE[dim], "") for dim in (2, 3)]
+        # Plackett is 2-D only: the two edge sizes, both as 2-D grids
+        out += [(m, "plackett", 2, (1.5,), n, "") for n in (N_EDGE[2], N_EDGE[3])]
+    return out
+
+
+def all_cases():
+    """cases() in the six-field form, then ext_cases(): a case's index is its row in the extension
+    fixture's event and candidate truths."""
+    return [c + (N_OF[c[2]], "") for c in cases()] + ext_cases()
+
+
+def ext_case_id(case):
+    model, copula, dim, params, n, variant = case
+    return case_id(case[:4]) + "-n%d" % n + ("-" + variant if variant else "")
+
+
+def gumbel_stiff(model, copula, dim, params):
+    """Gumbel cases whose one-ulp conditioning figure stays above 1e-15 of the slab's sum |mass|: three
+    axes at theta >= 4 (x_i^theta carries an ulp of u_i theta-fold on each axis) -- for GARCH under every
+    row set of SIGMA_CANDIDATES (tests/test_node_reference_ext_cpu.py asserts it) -- and, for MSM, whose
+    marginal inputs are the filter's and not chosen, also the 2-D survival kind at the cap theta = 16
+    (GARCH meets 1e-15 there on the equal rows, gumbel_sigma_rows)."""
+    if copula not in GUMBEL_KINDS:
+        return False
+    return (dim == 3 and params[0] >= 4.0) or (model == "msm" and copula == "gumbel_survival" and params[0] >= 16.0)
+
+
+def gumbel_sigma_rows(copula, dim, params):
+    if dim == 3:
+        return SIGMA_3D
+    return SIGMA_2D_EQUAL if copula == "gumbel_survival" and params[0] >= 16.0 else SIGMA_2D
+
+
+def msm_key(dim, n):
+    """Fixture prefix of the MSM filter outputs of a shape: node_kat.kat's for the base shapes."""
+    return "msm%d" % dim if n == N_OF[dim] else "msm%d_n%d" % (dim, n)
+
+
+def not_rank1(pi):
+    """pi (T, Q) with entry 0 of every date scaled by NR1_FACTOR and the row renormalised, in float64
+    steps whose order is fixed (a sequential sum), so every machine gets the same bits."""
+    out = np.array(pi, dtype=np.float64, copy=True)
+    out[:, 0] = out[:, 0] * NR1_FACTOR
+    for t in range(out.shape[0]):
+        s = 0.0
+        for v in out[t]:
+            s = s + float(v)
+        out[t] = out[t] / s
+    return out
+
+
+def ext_problem_inputs(case, z):
+    """Problem(...) arguments of a six-field case; z: a dict holding the MSM filter outputs the case
+    reads (msm_key: both fixtures merged)."""
+    from oracle import forecast as F
+    model, copula, dim, params, n, variant = case
+    w = np.full(dim, 1.0 / dim)
+    cp = float(params[0]) if copula == "plackett" else np.array(params, dtype=np.float64)
+    if model == "msm":
+        x, step = F.x_grid(n, "msm")
+        k = msm_key(dim, n)
+        uvs, pi = z[k + "_uvs"], z[k + "_pi"]
+        if variant == "nr1":
+            pi = not_rank1(pi)
+        return dict(model="msm", copula=copula, dim=dim, x_values=x, step=step, densities=F.msm_densities(uvs, x),
+                    combos=F.vol_combinations(dim, uvs.shape[1]), weights=w, copula_params=cp,
+                    per_date=(z[k + "_fbs"], pi), unique_vol_states=uvs)
+    assert variant == ""
+    x, step = F.x_grid(n, "garch")
+    rows = gumbel_sigma_rows(copula, dim, params) if copula in GUMBEL_KINDS else sigma_rows(copula, dim, params)
+    return dict(model=model, copula=copula, dim=dim, x_values=x, step=step, densities=np.ones((dim, 1, n)),
+                combos=np.zeros((1, dim)), weights=w, copula_params=cp, per_date=rows, unique_vol_states=None)
+
+
+def events(x, dim):
+    """[(axis, name, (lo, hi))] in grid units: per axis a stress event (-inf, x[n // 3]] and a band
+    (x[n // 4], x[3 n // 4]]."""
+    n = x.size
+    out = []
+    for c in range(dim):
+        out += [(c, "stress", (-INF, float(x[n // 3]))), (c, "band", (float(x[n // 4]), float(x[3 * n // 4])))]
+    return out
+
+
+def case_digest(case, z):
+    """SHA-256 of everything a six-field case's truths are computed from: the copula parameters, the
+    grid, the per-date inputs, the slabs, the events and the candidate weight vectors on offer."""
+    kw = ext_problem_inputs(case, z)
+    dim = case[2]
+    per = kw["per_date"] if case[0] == "msm" else (kw["per_date"],)
+    parts = [np.ravel(np.asarray(case[3], dtype=np.float64)), kw["x_values"], np.ravel(kw["step"]), kw["weights"],
+             np.ravel(kw["densities"])] + [np.ravel(a) for a in per]
+    if case[0] == "msm":
+        parts.append(np.ravel(kw["unique_vol_states"]))
+    parts += [np.ravel(slabs(dim)), np.ravel([b for _, _, b in events(kw["x_values"], dim)]),
+              np.ravel(PORT_UNEQUAL[dim]), np.ravel(PORT_SIGNED[dim])]
+    return digest(np.concatenate([np.asarray(p, dtype=np.float64) for p in parts]))
+
+
+# candidate weight vectors of the batched-weights pass: the plan's own, an unequal one, and one with a
+# zero or negative secondary weight -- the first of the alternatives under which every slab keeps a member
+# node on every date (the generator decides and stores the vectors; a zero weight leaves one axis' grid
+# to meet the narrow slab alone)
+PORT_UNEQUAL = {2: (0.7, 0.3), 3: (0.5, 0.3, 0.2)}
+PORT_SIGNED = {2: ((1.0, 0.0), (0.8, -0.2)), 3: ((0.6, 0.0, 0.4), (0.7, 0.5, -0.2))}

@@ -69,6 +69,20 @@ TIERS = {
     # two kernels built on it), cvq_quad_kernels.h:227-229 -- whatever the plan's strategy
     ("moments", "student", False): "precise", ("moments", "student", True): "precise",
     ("moments", "gaussian", False): "precise", ("moments", "plackett", False): "precise",
+    # the conditional and batched-weights passes (tests/test_node_ext_gpu.py): their own copies of the slab-row
+    # core, make_row / outer_B / node_value at cvq_conditional_kernels.h:170-178 and
+    # cvq_portfolio_kernels.h:189-197 -- node_value again, whatever the plan's strategy
+    ("cond", "student", False): "precise", ("cond", "student", True): "precise",
+    ("cond", "gaussian", False): "precise", ("cond", "plackett", False): "precise",
+    ("port", "student", False): "precise", ("port", "student", True): "precise",
+    ("port", "gaussian", False): "precise", ("port", "plackett", False): "precise",
+    # the Gumbel kinds (both under "gumbel"; SORTED only, cvq_plan.hip:1348): a SORTED slab of rank-1 dates
+    # takes the record path, node_fast at cvq_sorted_kernels.h:578-594 -- log_node / exp_node inside, the outer
+    # exponential exp2_node7; dates whose pi_t is not rank 1 take node_generic -> node_value (:599-), as do the
+    # moment, attribution, quantile, conditional and batched-weights kernels: cvq_quad_kernels.h:190-204,
+    # log_node / exp_node only.  Their bars: tests/gumbel_node_reference.py, stored in node_kat_ext.kat
+    ("sorted", "gumbel", False): "fast", ("sorted-generic", "gumbel", False): "precise",
+    ("moments", "gumbel", False): "precise", ("cond", "gumbel", False): "precise", ("port", "gumbel", False): "precise",
 }
 FAMILY = {"prefix": "prefix", "direct": "direct", "compact": "direct", "sorted": "sorted", "sweep": "sorted"}
 
@@ -195,3 +209,11 @@ def test_tier_table_is_complete():
     assert bar_of("sorted", "student", 2, (127.0, 0.5))[1] == "fast"        # node_m = 129 > 128: the general power
     assert bar_of("sorted", "student", 2, (126.0, 0.5))[1] == "precise"
     assert bar_of("direct", "student", 2, (5.364, 0.5))[1] == "precise"
+    # the conditional and batched-weights passes sit in the moments tier for every copula; the Gumbel kinds
+    # have SORTED instances only (their bars come from the second fixture: tests/test_node_ext_gpu.py)
+    for copula, general in (("student", False), ("student", True), ("gaussian", False), ("plackett", False),
+                            ("gumbel", False)):
+        assert TIERS[("cond", copula, general)] == TIERS[("port", copula, general)] == TIERS[("moments", copula, general)]
+    assert TIERS[("sorted", "gumbel", False)] == "fast" and TIERS[("sorted-generic", "gumbel", False)] == "precise"
+    assert not any(fam in ("prefix", "direct") and copula == "gumbel" for fam, copula, _ in TIERS)
+    assert all(t in ("precise", "fast") for t in TIERS.values())
