@@ -456,7 +456,9 @@ int32_t cvq_garch_loglik_pq(int32_t device, int32_t p, int32_t q, const double* 
  * k_direct) and pow_fast incl. SORTED's exp2_node7(ex log2(e) log_node_fast(b)) power
  * (cvq_sorted_kernels.h: SORTED and SWEEP slabs).  Not reached by either tier:
  * COMPACT's own copy of that fast power (cvq_compact_kernels.h), which runs in its solve
- * only and is held through the solves' VaR parity alone. */
+ * only.  It, and every strategy's solve path with it (level loops, block tails, generic
+ * kernels), is held to the same longdouble reference by obj_var probes of cvq_solve_local
+ * (tests/test_solve_probes_gpu.py; DESIGN.md §5 "Solve-path probes"). */
 int32_t cvq_special(int32_t device, int32_t fn, double nu, const double* x, int64_t n,
                     double* out, int32_t mem);
 

@@ -57,9 +57,23 @@ TIERS = {
     # DIRECT and COMPACT slabs both run k_direct (cvq_plan.hip launch_slab: "COMPACT: slabs of arbitrary
     # bounds run k_direct"): pow_node_t, cvq_direct_kernels.h:20-41 and :155 (integer: rcp + one Newton
     # step, ~1e-15; PM == 0: pow_node); Gaussian / Plackett: node_value, cvq_quad_kernels.h:229.
-    # COMPACT's own fast power (cvq_compact_kernels.h:350-356) runs in its solve only, not in a slab.
+    # COMPACT's own fast power (cvq_compact_kernels.h:350-356) runs in its solve only, not in a slab: the
+    # "compact-solve" rows below, held by the obj_var probes of tests/test_solve_probes_gpu.py.
     ("direct", "student", False): "precise", ("direct", "student", True): "precise",
     ("direct", "gaussian", False): "precise", ("direct", "plackett", False): "precise",
+    # the solve kernels (tests/test_solve_probes_gpu.py; DIRECT's and PREFIX's solves run their slabs' node code:
+    # cvq_direct_kernels.h k_direct's solve loop, cvq_quad_kernels.h k_solve_prefix over k_mass's table).
+    # k_compact's solve: fast_f, cvq_compact_kernels.h:343-373 -- nu = 6 (PM 8) rcp + one Newton step then two
+    # squarings (:346-350); other integer nu pow_node_t (:356); fitted nu and node_m > 128
+    # exp2_node7(ex log2(e) log_node_fast(b)) (:352-355); Gaussian exp2_node7 of the folded row constants
+    # (:358-361, fast_row_consts :309-313); Plackett rcp + two Newton steps (:363-371); dates deferred to its
+    # generic kernel: node_value (:377-394)
+    ("compact-solve", "student", False): "precise", ("compact-solve", "student", True): "fast",
+    ("compact-solve", "gaussian", False): "fast", ("compact-solve", "plackett", False): "precise",
+    # k_sorted's solve loop (:937-973), block tail (:1012), one-wave tail (:1077) and SWEEP's passes (:815) sum
+    # the same node_fast / node_generic lambdas (:554, :599) as its slab (:746): the sorted tier
+    ("sorted-solve", "student", False): "precise", ("sorted-solve", "student", True): "fast",
+    ("sorted-solve", "gaussian", False): "fast", ("sorted-solve", "plackett", False): "precise",
     # SORTED and SWEEP slabs: node_fast, cvq_sorted_kernels.h:554-577 -- Gaussian exp2_node7
     # (:130-133, 4.0e-11); Student pow_fast (:135-160): fitted nu exp2_node7(ex log2(e) log_node_fast(b)),
     # integer nu squarings + rcp + one Newton step (~1e-15); Plackett: rcp + Newton (:560-565)
@@ -209,6 +223,13 @@ def test_tier_table_is_complete():
     assert bar_of("sorted", "student", 2, (127.0, 0.5))[1] == "fast"        # node_m = 129 > 128: the general power
     assert bar_of("sorted", "student", 2, (126.0, 0.5))[1] == "precise"
     assert bar_of("direct", "student", 2, (5.364, 0.5))[1] == "precise"
+    # the solve kernels' families (tests/test_solve_probes_gpu.py): COMPACT's solve has its own fast power and
+    # Gaussian exponential, which its slab (k_direct) has not; SORTED's solve sits in its slab's tier
+    for copula, params in (("student", (6.0, 0.5)), ("student", (5.364, 0.5)), ("student", (127.0, 0.5)),
+                           ("gaussian", (0.5,)), ("plackett", (1.5,))):
+        assert bar_of("sorted-solve", copula, 2, params) == bar_of("sorted", copula, 2, params)
+        assert bar_of("compact-solve", copula, 2, params) == bar_of("sorted", copula, 2, params)
+    assert bar_of("compact-solve", "student", 2, (7.0, 0.5))[1] == "precise"
     # the conditional and batched-weights passes sit in the moments tier for every copula; the Gumbel kinds
     # have SORTED instances only (their bars come from the second fixture: tests/test_node_ext_gpu.py)
     for copula, general in (("student", False), ("student", True), ("gaussian", False), ("plackett", False),
