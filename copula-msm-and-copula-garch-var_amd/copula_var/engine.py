@@ -571,6 +571,64 @@ class QuadraturePlan:
                                                 lv.size, C.c_void_p(var_ptr), C.c_void_p(es_ptr or 0),
                                                 C.c_void_p(m0_ptr or 0), N.MEM_DEVICE), "cvq_portfolio_quantiles")
 
+    # ------------------------------------------------------------ quantiles under per-date records
+    def _dynamic_inputs(self, levels, copula_params, weights, ptf_mean):
+        """The host arrays of one cvq_dynamic_quantiles call: (levels, params or None, weights or
+        None, means); a scalar ptf_mean serves every date."""
+        lv = N.f64(np.atleast_1d(np.asarray(levels, dtype=np.float64)))
+        if lv.ndim != 1:
+            raise ValueError("levels must be a sequence of numbers")
+        cp = w = None
+        if copula_params is not None:
+            cp = N.f64(copula_params)
+            if cp.ndim == 1 and self._cp.size == 1:
+                cp = N.f64(cp.reshape(-1, 1))
+            if cp.shape != (self.T, self._cp.size):
+                raise ValueError(f"copula_params must have shape ({self.T}, {self._cp.size})")
+        if weights is not None:
+            w = N.f64(weights)
+            if w.shape != (self.T, self.dim):
+                raise ValueError(f"weights must have shape ({self.T}, {self.dim})")
+        pm = N.f64(np.broadcast_to(np.asarray(ptf_mean, dtype=np.float64), (self.T,)))
+        return lv, cp, w, pm
+
+    def dynamic_scratch(self, n_levels: int) -> int:
+        """Bytes of device scratch one cvq_dynamic_quantiles call of n_levels levels takes."""
+        b = C.c_int64()
+        N.check(N.lib().cvq_dynamic_scratch(self._h, int(n_levels), C.byref(b)), "cvq_dynamic_scratch")
+        return int(b.value)
+
+    def dynamic_quantiles(self, levels, copula_params=None, weights=None, ptf_mean=0.0, min_var=-7.5, max_var=0.0,
+                          lower=-100.0, tolerance=1e-6) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(var, es, m0), each (T, L): `quantiles` where every date has copula parameters, weights
+        and a mean of its own.  copula_params (T, n_copula_params) in the constructor's packing
+        (a (T,) vector for the one-parameter copulas), weights (T, dim) in the constructor's
+        convention (quirk Q10; weights[t, 0] > 0), ptf_mean a scalar or (T,); None keeps the plan's
+        own on every date.  [t] is bit for bit what `quantiles` returns on a plan built with date
+        t's parameters and weights and given date t alone.  The copula kind and the Student nu stay
+        the plan's (copula_params[t, 0] must repeat nu).  ValueError names the first bad date."""
+        lv, cp, w, pm = self._dynamic_inputs(levels, copula_params, weights, ptf_mean)
+        args = solve_args(0.0, min_var=min_var, max_var=max_var, lower=lower, tolerance=tolerance)
+        out = [np.empty((self.T, lv.size)) for _ in range(3)]
+        N.check(N.lib().cvq_dynamic_quantiles(self._h, C.byref(args), N.ptr(cp) if cp is not None else None,
+                                              N.ptr(w) if w is not None else None, N.ptr(pm), N.ptr(lv), lv.size,
+                                              N.ptr(out[0]), N.ptr(out[1]), N.ptr(out[2]), N.MEM_HOST),
+                "cvq_dynamic_quantiles")
+        return out[0], out[1], out[2]
+
+    def dynamic_quantiles_device(self, args: N.CvqSolveArgs, levels, var_ptr: int, es_ptr: Optional[int] = None,
+                                 m0_ptr: Optional[int] = None, copula_params=None, weights=None,
+                                 ptf_mean=None) -> None:
+        """dynamic_quantiles into device buffers [T][L] (args: min_var, max_var, lower and tolerance
+        are read, and ptf_mean where ptf_mean is None; the per-date arrays and levels stay on the
+        host and may be dropped on return), in stream order: no host synchronisation."""
+        lv, cp, w, pm = self._dynamic_inputs(levels, copula_params, weights, 0.0 if ptf_mean is None else ptf_mean)
+        N.check(N.lib().cvq_dynamic_quantiles(self._h, C.byref(args), N.ptr(cp) if cp is not None else None,
+                                              N.ptr(w) if w is not None else None,
+                                              N.ptr(pm) if ptf_mean is not None else None, N.ptr(lv), lv.size,
+                                              C.c_void_p(var_ptr), C.c_void_p(es_ptr or 0), C.c_void_p(m0_ptr or 0),
+                                              N.MEM_DEVICE), "cvq_dynamic_quantiles")
+
     # ------------------------------------------------------------ device-resident solve
     def solve_device(self, args: N.CvqSolveArgs, var_ptr: int, check: bool = False) -> Optional[int]:
         """calc_var into a device buffer.  check=False: in stream order, no host

@@ -20,7 +20,7 @@ import sys
 import numpy as np
 import pandas as pd
 
-from . import portfolios
+from . import dynamic, portfolios
 from .data_loader.load_data import SharedCacheIndexReturns, load_returns_csv
 from .utils.calc_var_class import ValueAtRiskCalcualtion
 from .utils.factory import ValueAtRiskCalculationFactory
@@ -84,6 +84,17 @@ def build_parser() -> argparse.ArgumentParser:
                          "(default 0.05) in one batched device call, and the candidate with the smallest expected "
                          "loss per date: wbest_<estimation>_<ticker>_<level> (that candidate's weight on the ticker) "
                          "and wbest_es_<estimation>_<level> columns in --out")
+    ap.add_argument("--rolling-copula", type=int, default=None, metavar="WINDOW",
+                    help="also compute the exact quantile and Expected Shortfall at the levels of --exact-levels "
+                         "under copula parameters refitted on the last WINDOW rows before each refit date "
+                         "(in-sample rows, then the realised out-of-sample rows; a Student nu stays fixed): "
+                         "dvar_<estimation>_<level> / des_<estimation>_<level> columns in --out, the parameter "
+                         "path in dparam_<estimation>_<k>")
+    ap.add_argument("--refit-every", type=int, default=21, metavar="STEP",
+                    help="out-of-sample dates between two refits of --rolling-copula (default 21)")
+    ap.add_argument("--drift-weights", action="store_true",
+                    help="the dvar / des columns follow a buy-and-hold portfolio: --weights on the first date, then "
+                         "drifting with the realised returns (with or without --rolling-copula)")
     return ap
 
 
@@ -99,7 +110,16 @@ def main(argv=None) -> int:
         raise SystemExit(f"--covar {a.covar}: not one of --tickers")
     if a.weight_grid is not None and a.weight_grid < 1:
         raise SystemExit("--weight-grid: STEPS must be >= 1")
-    out, runs, es, esc, exact, covar, wbest = {}, {}, {}, {}, {}, {}, {}
+    dynamic_on = a.rolling_copula is not None or a.drift_weights
+    if dynamic_on and not a.exact_levels:
+        raise SystemExit("--rolling-copula, --refit-every and --drift-weights need --exact-levels")
+    if a.refit_every != 21 and a.rolling_copula is None:
+        raise SystemExit("--refit-every needs --rolling-copula")
+    if a.rolling_copula is not None and a.rolling_copula < 2:
+        raise SystemExit("--rolling-copula: WINDOW must be >= 2")
+    if a.refit_every < 1:
+        raise SystemExit("--refit-every: STEP must be >= 1")
+    out, runs, es, esc, exact, covar, wbest, dyn = {}, {}, {}, {}, {}, {}, {}, {}
     for est in a.estimation:
         calc = ValueAtRiskCalculationFactory.create_var_calculator(copula_type=a.copula, estimation_type=est)
         kw = {"k": a.k} if est == "msm" else {}
@@ -137,6 +157,23 @@ def main(argv=None) -> int:
                 print(f"{est}/{a.copula}: candidate " + ", ".join(f"{t} {x:g}" for t, x in zip(a.tickers, wv)) +
                       ": mean ES " + ", ".join(f"{lv:g}: {mean_es[p, i]:.4f}" for i, lv in enumerate(covar_levels)),
                       file=sys.stderr)
+        if dynamic_on:
+            run = runs[est]
+            T = run.plan.T
+            path = np.tile(run.copula_params, (T, 1))
+            if a.rolling_copula is not None:
+                path, info = run.rolling_copula_params(a.rolling_copula, a.refit_every)
+                print(f"{est}/{a.copula}: rolling copula, window {a.rolling_copula}: {len(info['refits'])} refits, "
+                      f"{len(info['failed'])} failed; parameters from "
+                      + ", ".join(f"{v:.4f}" for v in path[0]) + " to " + ", ".join(f"{v:.4f}" for v in path[-1]),
+                      file=sys.stderr)
+            wt = None
+            if a.drift_weights:
+                wt = dynamic.drift_weights(run.out_sample_data.to_numpy(dtype=np.float64)[:T], weights)
+            dyn[est] = run.calc_dynamic_quantiles(a.exact_levels, copula_params=path, weights=wt) + (path,)
+            for i, lv in enumerate(a.exact_levels):
+                print(f"{est}/{a.copula}: mean dynamic VaR at {lv:g}: {np.nanmean(dyn[est][0][:, i]):.4f}",
+                      file=sys.stderr)
     first = runs[a.estimation[0]]
     portfolio = first.out_sample_data.mean(axis=1).to_numpy()                    # main.py:73
     if a.out:
@@ -157,6 +194,12 @@ def main(argv=None) -> int:
                 for i, lv in enumerate(covar_levels):
                     for name, arr in zip(("covar", "coes", "dcovar"), covar[k]):
                         cols[f"{name}_{k}_{a.covar}_{lv:g}"] = arr[:, i]
+            if k in dyn:
+                for i, lv in enumerate(a.exact_levels):
+                    cols[f"dvar_{k}_{lv:g}"] = dyn[k][0][:, i]
+                    cols[f"des_{k}_{lv:g}"] = dyn[k][1][:, i]
+                for j in range(dyn[k][2].shape[1]):
+                    cols[f"dparam_{k}_{j}"] = dyn[k][2][:, j]
             if k in wbest:
                 for i, lv in enumerate(covar_levels):
                     for c, ticker in enumerate(a.tickers):

@@ -182,6 +182,51 @@ class ValueAtRiskCalcualtion:
         var, es, self.last_tail_mass = self.plan.portfolio_quantiles(w, levels, ptf_mean)
         return var, es
 
+    def dynamic_ptf_mean(self, weights=None):
+        """The portfolio mean of every date: the loader's formula (load_data.py:128) applied to
+        that date's weights (T, dim); None: the constructor's own mean on every date."""
+        if weights is None:
+            return float(self.ptf_mean)
+        means = np.array([self.mean_returns[tk] for tk in self.mean_returns], dtype=np.float64)
+        return np.array([np.sum(means * wt) for wt in np.asarray(weights, dtype=np.float64)])
+
+    def calc_dynamic_quantiles(self, levels=(0.05,), copula_params=None, weights=None):
+        """(var, es), each (T, L): calc_quantiles where every date has copula parameters and weights
+        of its own (no reference counterpart) -- a refitted or DCC-style dependence path, a
+        buy-and-hold portfolio whose weights drift (copula_var.dynamic builds both).
+        copula_params (T, n) in this run's own packing (self.copula_params; a Student nu must stay
+        the run's), weights (T, dim) in the constructor's convention (quirk Q10, see
+        calc_portfolio_quantiles; weights[t, 0] > 0); None keeps the run's own.  Row t is what
+        calc_quantiles returns for date t from a run constructed with those parameters and
+        weights, its portfolio mean included.  All dates in one device call.  The masses found
+        below each quantile are kept in last_tail_mass (T, L)."""
+        if weights is not None:
+            weights = np.asarray(weights, dtype=np.float64)
+            if weights.shape != (self.plan.T, self.dim):
+                raise ValueError(f"weights must have shape ({self.plan.T}, {self.dim})")
+        var, es, self.last_tail_mass = self.plan.dynamic_quantiles(levels, copula_params, weights,
+                                                                   self.dynamic_ptf_mean(weights))
+        return var, es
+
+    def oos_pits(self):
+        """(u, pdf), each (T, dim): the forecast marginals' CDF and density at the realised centred
+        return of every out-of-sample date (copula_var.dynamic.oos_pits on this run's forecasts)."""
+        from ..data_loader.load_data import centred_series
+        from ..dynamic import oos_pits
+        r = centred_series(self.rolling_windows_dict, list(self.tickers))
+        T = self.plan.T
+        return oos_pits(self.VaRCalculationMethod.model_kind, self.integrations_params_t,
+                        self.integrations_params_static, r[self.in_sample_data_num:self.in_sample_data_num + T])
+
+    def rolling_copula_params(self, window, every=21):
+        """(params (T, n), info): this run's copula refitted every `every` out-of-sample dates on the
+        last `window` rows of [in-sample marginals, then the out-of-sample PITs before the date]
+        (copula_var.dynamic.rolling_copula_params); a Student nu stays the run's."""
+        from ..dynamic import rolling_copula_params
+        u, pdf = self.oos_pits()
+        return rolling_copula_params(self.VaRCalculationMethod.copula_kind, self.marginals, self.densities, u, pdf,
+                                     window, every, static_params=self.copula_params, device=self.device)
+
     def _asset_index(self, asset) -> int:
         if isinstance(asset, str):
             tickers = list(self.tickers)

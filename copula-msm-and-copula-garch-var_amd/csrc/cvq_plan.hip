@@ -172,6 +172,15 @@ struct cvq_plan {
     // sums, state and cuts, then the call's weight records; the marginal tables are the moments'
     size_t capPort = 0;
     double* d_pwork = nullptr;
+    // per-date-record quantiles (cvq_dynamic_quantiles): the call's date records and means, then
+    // per-(date, level) partial sums, state and cuts; the marginal tables are the moments'.  The
+    // records travel through pinned host buffers, so a device-mode call never waits on the stream:
+    // a buffer is taken again once the event behind its upload has completed.
+    int n_cp = 0;                // cvq_static.n_copula_params: the stride of copula_params_t
+    size_t capDyn = 0;
+    double* d_dwork = nullptr;
+    struct DynStage { double* h; size_t cap; hipEvent_t done; };
+    std::vector<DynStage> dyn_stage;
     unsigned long long* d_stamps = nullptr;   // diagnostic phase stamps (CVQ_STAMPS=1)
     bool count_nodes = false;    // cvq_plan_count_nodes: solves record their node counts (stamps)
     bool nodes_valid = false;    // the last solve recorded them
@@ -895,6 +904,13 @@ int launch_portfolios(const StaticDev& S, long long T, hipStream_t stream, const
                       double* tA, double* tB, double* work, const double* wrec, const double* mean, int P,
                       const double* alpha, int L, int K, double min_var, double max_var, double lower,
                       double* var_out, double* es_out, double* m0_out, size_t abi);
+size_t dynamic_scratch(int dim, int nrows, long long T, int L);                        // cvq_dynamic.hip
+size_t dynamic_upload_doubles(long long T);
+size_t dynamic_mean_offset(long long T);
+void dynamic_pack(double* recs, long long t, double theta, double term1, const double* Ri, const double* w);
+int launch_dynamic(const StaticDev& S, long long T, hipStream_t stream, const double* a, const double* pi,
+                   double* tA, double* tB, double* work, const double* alpha, int L, int K, double min_var,
+                   double max_var, double lower, double* var_out, double* es_out, double* m0_out, size_t abi);
 size_t attrib_scratch(int dim, int nrows);                                            // cvq_attrib.hip
 int launch_attrib(const StaticDev& S, long long T, hipStream_t stream, const double* a, const double* pi, double* tA,
                   double* tB, double* part, const double* bounds, const double* var, double lower, double ptf_mean,
@@ -1292,13 +1308,101 @@ double invert(const double* R, int d, double* Ri) {
     return det;
 }
 
+// The copula constants of the generic node path, computed as the reference does on the host, for
+// one parameter vector cp (cvq_static.copula_params' packing; nu = cp[0] of a Student copula):
+// theta (Plackett, Gumbel), or the inverse correlation Ri and the density constant term1 (Gaussian,
+// Student).  cvq_plan_create and cvq_dynamic_quantiles both take them from here, so a date's record
+// holds the bits a plan created with that date's parameters would.  Returns invert()'s determinant
+// (1 for the kinds without a correlation matrix).
+struct CopulaConst {
+    double theta = 0.0, term1 = 0.0;
+    double Ri[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+};
+double copula_constants(int copula, int d, const double* cp, CopulaConst* out) {
+    if (copula == CVQ_PLACKETT || copula == CVQ_GUMBEL || copula == CVQ_GUMBEL_SURVIVAL) {
+        out->theta = cp[0];
+        return 1.0;
+    }
+    const int base = copula == CVQ_STUDENT ? 1 : 0;
+    double R[9];
+    int k = 0;
+    for (int i = 0; i < d; ++i) R[i * d + i] = 1.0;
+    for (int i = 0; i < d; ++i)                 // triu / tril fill (student_estimation.py:50-54)
+        for (int j = i + 1; j < d; ++j) { R[i * d + j] = R[j * d + i] = cp[base + k]; ++k; }
+    const double det = invert(R, d, out->Ri);
+    if (copula == CVQ_STUDENT) {
+        const double nu = cp[0];
+        out->term1 = std::tgamma((nu + d) / 2) /
+                     (std::tgamma(nu / 2) * std::pow(nu * M_PI, d / 2.0) * std::sqrt(det));   // student.py:138
+    } else {
+        out->term1 = 1 / (std::sqrt(std::pow(2 * M_PI, d) * det));                              // gaussian.py:107
+    }
+    return det;
+}
+
+// The exact-reciprocal rule of the inner-axis weight: 1 / w0 where w0 = 2^e (frexp mantissa 1/2)
+// and 1 / w0 is a normal double, else 0 (divide), as cvq_plan_create forms StaticDev::w0_inv.
+double w0_reciprocal(double w0) {
+    int e2 = 0;
+    const double m2 = std::frexp(w0, &e2);
+    return (m2 == 0.5 && std::isnormal(1.0 / w0)) ? 1.0 / w0 : 0.0;
+}
+
+// A pinned host buffer of at least `need` doubles whose last upload has completed (a new one
+// where every buffer is still in flight or too small).
+int dyn_stage_take(cvq_plan* p, size_t need, cvq_plan::DynStage** out) {
+    for (auto& s : p->dyn_stage)
+        if (s.cap >= need && hipEventQuery(s.done) == hipSuccess) { *out = &s; return CVQ_OK; }
+    (void)hipGetLastError();                       // hipErrorNotReady of a buffer in flight
+    for (size_t i = p->dyn_stage.size(); i-- > 0;) {      // the idle ones are too small: drop them
+        auto& s = p->dyn_stage[i];
+        if (hipEventQuery(s.done) != hipSuccess) continue;
+        (void)hipEventDestroy(s.done);
+        (void)hipHostFree(s.h);
+        p->dyn_stage.erase(p->dyn_stage.begin() + (long)i);
+    }
+    (void)hipGetLastError();
+    cvq_plan::DynStage s{nullptr, need, nullptr};
+    CVQ_HIP_CHECK(hipHostMalloc((void**)&s.h, need * sizeof(double), hipHostMallocDefault));
+    hipError_t e = hipEventCreateWithFlags(&s.done, hipEventDisableTiming);
+    if (e != hipSuccess) { (void)hipHostFree(s.h); CVQ_HIP_CHECK(e); }
+    p->dyn_stage.push_back(s);
+    *out = &p->dyn_stage.back();
+    return CVQ_OK;
+}
+
+// Per-date-record quantiles: the moments' table scratch + a work buffer of their own whose head
+// takes the records, then the pass schedule (timed with the exact quantiles, kind 6).
+// up: host, dynamic_upload_doubles(T) doubles (records, then means); copied before returning.
+int run_dynamic(cvq_plan* p, const cvq_solve_args& a, int K, const double* up, const double* levels, int L,
+                double* var, double* es, double* m0) {
+    CVQ_HIP_CHECK(hipSetDevice(p->device));
+    int rc = ensure_moments(p);
+    if (rc) return rc;
+    const size_t need = dynamic_scratch(p->S.dim, p->S.nrows, p->T, L);
+    if (need > p->capDyn) {
+        p->capDyn = 0;
+        if ((rc = dev_alloc(&p->d_dwork, need))) return rc;
+        p->capDyn = need;
+    }
+    const size_t nup = dynamic_upload_doubles(p->T);
+    cvq_plan::DynStage* stage = nullptr;
+    if ((rc = dyn_stage_take(p, nup, &stage))) return rc;
+    std::memcpy(stage->h, up, nup * sizeof(double));
+    TimedScope ts(p, TK_QUANTILES);
+    CVQ_HIP_CHECK(hipMemcpyAsync(p->d_dwork, stage->h, nup * sizeof(double), hipMemcpyHostToDevice, p->stream));
+    CVQ_HIP_CHECK(hipEventRecord(stage->done, p->stream));
+    return launch_dynamic(p->S, p->T, p->stream, p->in_a, p->in_pi, p->d_mA, p->d_mB, p->d_dwork, levels, L, K,
+                          a.min_var, a.max_var, a.lower, var, es, m0, kernel_abi_key());
+}
+
 }  // namespace
 
 // =================================================================== C ABI
 extern "C" {
 
 const char* cvq_last_error(void) { return g_err.c_str(); }
-int32_t cvq_version(void) { return 10700; }
+int32_t cvq_version(void) { return 10800; }
 
 int32_t cvq_device_count(int32_t* count) {
     CVQ_REQUIRE(count != nullptr, CVQ_ERR_INVALID, "count is NULL");
@@ -1384,41 +1488,36 @@ int32_t cvq_plan_create(const cvq_static* s, int32_t device, cvq_plan** out) {
     S.w1 = s->weights[1];
     S.w2 = s->dim == 3 ? s->weights[2] : 0.0;
 
-    // copula constants, computed as the reference does on the host
+    // copula constants, computed as the reference does on the host (copula_constants)
     const int d = s->dim;
     const double* cp = s->copula_params;
+    p->n_cp = s->n_copula_params;
     if (s->copula == CVQ_PLACKETT) {
         CVQ_REQUIRE(s->n_copula_params >= 1, CVQ_ERR_INVALID, "Plackett needs theta");
-        S.theta = cp[0];
-    } else if (gumbel) {
-        S.theta = cp[0];
-    } else {
+    } else if (!gumbel) {
         const int nrho = d * (d - 1) / 2;
         const int base = s->copula == CVQ_STUDENT ? 1 : 0;
         CVQ_REQUIRE(s->n_copula_params == base + nrho, CVQ_ERR_INVALID, "wrong copula parameter count");
-        double R[9];
-        int k = 0;
-        for (int i = 0; i < d; ++i) R[i * d + i] = 1.0;
-        for (int i = 0; i < d; ++i)                 // triu / tril fill (student_estimation.py:50-54)
-            for (int j = i + 1; j < d; ++j) { R[i * d + j] = R[j * d + i] = cp[base + k]; ++k; }
-        const double det = invert(R, d, S.Ri);
-        if (s->copula == CVQ_STUDENT) {
-            const double nu = cp[0];
-            CVQ_REQUIRE(nu > 0.0, CVQ_ERR_INVALID, "nu must be > 0");
-            S.nu = nu;
-            S.inv_nu = 1.0 / nu;
-            S.term1 = std::tgamma((nu + d) / 2) /
-                      (std::tgamma(nu / 2) * std::pow(nu * M_PI, d / 2.0) * std::sqrt(det));   // student.py:138
-            S.g_uni = std::tgamma((nu + 1) / 2) / (std::sqrt(nu * M_PI) * std::tgamma(nu / 2)); // :164
-            S.inv_g_uni = 1.0 / S.g_uni;
-            S.node_ex = -(nu + d) / 2;
-            S.uni_ex = -(nu + 1) / 2;
-            S.uni_m = half_power_code(nu + 1, 16.0);
-            S.node_m = half_power_code(-2.0 * S.node_ex, 128.0);
-            if (int rc2 = make_tconst(nu, &S.tk, &p->d_cf)) { cvq_plan_destroy(p); return rc2; }
-        } else {
-            S.term1 = 1 / (std::sqrt(std::pow(2 * M_PI, d) * det));                              // gaussian.py:107
-        }
+    }
+    {
+        CopulaConst cc;
+        copula_constants(s->copula, d, cp, &cc);
+        S.theta = cc.theta;
+        S.term1 = cc.term1;
+        for (int i = 0; i < 9; ++i) S.Ri[i] = cc.Ri[i];
+    }
+    if (s->copula == CVQ_STUDENT) {
+        const double nu = cp[0];
+        CVQ_REQUIRE(nu > 0.0, CVQ_ERR_INVALID, "nu must be > 0");
+        S.nu = nu;
+        S.inv_nu = 1.0 / nu;
+        S.g_uni = std::tgamma((nu + 1) / 2) / (std::sqrt(nu * M_PI) * std::tgamma(nu / 2)); // :164
+        S.inv_g_uni = 1.0 / S.g_uni;
+        S.node_ex = -(nu + d) / 2;
+        S.uni_ex = -(nu + 1) / 2;
+        S.uni_m = half_power_code(nu + 1, 16.0);
+        S.node_m = half_power_code(-2.0 * S.node_ex, 128.0);
+        if (int rc2 = make_tconst(nu, &S.tk, &p->d_cf)) { cvq_plan_destroy(p); return rc2; }
     }
 
     // static tables
@@ -1553,8 +1652,9 @@ int32_t cvq_plan_destroy(cvq_plan* p) {
                     (void*)p->d_mA, (void*)p->d_mB, (void*)p->d_mpart, (void*)p->d_qwork, (void*)p->d_apart,
                     (void*)p->d_cutfix, (void*)p->d_kcut, (void*)p->d_fpair, (void*)p->d_ccount, (void*)p->d_tlist, (void*)p->d_tvs, (void*)p->d_defer, (void*)p->d_vstar, (void*)p->d_bucket, (void*)p->d_sidx, (void*)p->d_svs,
                     (void*)p->d_tree, (void*)p->d_pass,
-                    (void*)p->d_pidx, (void*)p->d_pvs, (void*)p->d_cwork, (void*)p->d_pwork})
+                    (void*)p->d_pidx, (void*)p->d_pvs, (void*)p->d_cwork, (void*)p->d_pwork, (void*)p->d_dwork})
         if (b) (void)hipFree(b);
+    for (auto& st : p->dyn_stage) { (void)hipEventDestroy(st.done); (void)hipHostFree(st.h); }
     if (p->own_stream) (void)hipStreamDestroy(p->own_stream);
     delete p;
     return CVQ_OK;
@@ -1970,6 +2070,99 @@ int32_t cvq_portfolio_scratch(const cvq_plan* p, int32_t n_portfolios, int32_t n
                 CVQ_ERR_INVALID, "n_portfolios must be in [1, CVQ_MAX_PORTFOLIOS], n_levels in [1, CVQ_MAX_LEVELS]");
     CVQ_REQUIRE(p->T > 0, CVQ_ERR_STATE, "cvq_set_dates must be called first");
     *bytes = (int64_t)(portfolio_scratch(p->S.dim, p->S.nrows, p->T, n_portfolios, n_levels) * sizeof(double));
+    return CVQ_OK;
+}
+
+int32_t cvq_dynamic_quantiles(cvq_plan* p, const cvq_solve_args* a, const double* copula_params_t,
+                              const double* weights_t, const double* ptf_mean_t, const double* levels,
+                              int32_t n_levels, double* var_out, double* es_out, double* m0_out, int32_t mem) {
+    cvq::DeviceScope device_scope;                 // the caller's current device, restored on return
+    // everything is checked on the host before any device work
+    CVQ_REQUIRE(p != nullptr && a != nullptr && levels != nullptr && var_out != nullptr, CVQ_ERR_INVALID,
+                "NULL argument");
+    CVQ_REQUIRE(n_levels >= 1 && n_levels <= CVQ_MAX_LEVELS, CVQ_ERR_INVALID, "n_levels must be in [1, CVQ_MAX_LEVELS]");
+    for (int l = 0; l < n_levels; ++l)
+        CVQ_REQUIRE(levels[l] > 0.0 && std::isfinite(levels[l]), CVQ_ERR_INVALID, "a level must be finite and > 0");
+    CVQ_REQUIRE(std::isfinite(a->min_var) && std::isfinite(a->max_var) && a->max_var > a->min_var, CVQ_ERR_INVALID,
+                "max_var must be above min_var");
+    CVQ_REQUIRE(a->tolerance > 0.0 && std::isfinite(a->tolerance), CVQ_ERR_INVALID, "tolerance must be > 0");
+    CVQ_REQUIRE(!(a->lower > a->min_var), CVQ_ERR_INVALID, "lower must not be above min_var");
+    CVQ_REQUIRE(ptf_mean_t != nullptr || std::isfinite(a->ptf_mean), CVQ_ERR_INVALID, "ptf_mean must be finite");
+    const double steps = std::ceil(std::log2((a->max_var - a->min_var) / a->tolerance));
+    CVQ_REQUIRE(steps <= (double)kMaxIters, CVQ_ERR_UNSUPPORTED, "bisection needs more than 62 iterations");
+    const int K = steps > 0.0 ? (int)steps : 0;
+    CVQ_REQUIRE(p->T > 0, CVQ_ERR_STATE, "cvq_set_dates must be called first");
+    const StaticDev& S = p->S;
+    const long long T = p->T;
+    const int d = S.dim, ncp = p->n_cp;
+    const int kind = S.copula == CVQ_GUMBEL && S.survival ? CVQ_GUMBEL_SURVIVAL : S.copula;
+    // the date records, each formed as cvq_plan_create forms the plan's own constants
+    std::vector<double> up(dynamic_upload_doubles(T));
+    double* mean = up.data() + dynamic_mean_offset(T);
+    const double own_w[4] = {S.w0, S.w1, S.w2, S.w0_inv};
+    for (long long t = 0; t < T; ++t) {
+        const auto at = [t] { return " at date " + std::to_string(t); };   // built on a failure only
+        CopulaConst cc;
+        cc.theta = S.theta;
+        cc.term1 = S.term1;
+        for (int i = 0; i < 9; ++i) cc.Ri[i] = S.Ri[i];
+        if (copula_params_t) {
+            const double* cp = copula_params_t + (size_t)t * ncp;
+            for (int i = 0; i < ncp; ++i)
+                CVQ_REQUIRE(std::isfinite(cp[i]), CVQ_ERR_INVALID, "a copula parameter must be finite" + at());
+            if (S.copula == CVQ_GUMBEL) {
+                CVQ_REQUIRE(cp[0] >= 1.0, CVQ_ERR_INVALID, "Gumbel theta must be >= 1" + at());
+                CVQ_REQUIRE(cp[0] <= 16.0, CVQ_ERR_UNSUPPORTED, "Gumbel theta must be <= 16" + at());
+            }
+            if (S.copula == CVQ_STUDENT) {
+                CVQ_REQUIRE(cp[0] > 0.0, CVQ_ERR_INVALID, "nu must be > 0" + at());
+                CVQ_REQUIRE(cp[0] == S.nu, CVQ_ERR_UNSUPPORTED,
+                            "the Student nu is fixed per plan (copula_params_t[t][0] must equal the plan's nu)" + at());
+            }
+            if (S.copula == CVQ_GAUSSIAN || S.copula == CVQ_STUDENT)
+                for (int i = S.copula == CVQ_STUDENT ? 1 : 0; i < ncp; ++i)
+                    CVQ_REQUIRE(std::fabs(cp[i]) < 1.0, CVQ_ERR_INVALID, "a correlation must lie inside (-1, 1)" + at());
+            cc = CopulaConst();
+            const double det = copula_constants(kind, d, cp, &cc);
+            CVQ_REQUIRE(det > 0.0, CVQ_ERR_INVALID, "the correlation matrix is not positive definite" + at());
+        }
+        double w[4] = {own_w[0], own_w[1], own_w[2], own_w[3]};
+        if (weights_t) {
+            const double* wt = weights_t + (size_t)t * d;
+            for (int i = 0; i < d; ++i) CVQ_REQUIRE(std::isfinite(wt[i]), CVQ_ERR_INVALID, "a weight must be finite" + at());
+            CVQ_REQUIRE(wt[0] > 0.0, CVQ_ERR_UNSUPPORTED,
+                        "weights_t[t][0] must be > 0 (the inner-axis division, Q10)" + at());
+            w[0] = wt[0];
+            w[1] = wt[1];
+            w[2] = d == 3 ? wt[2] : 0.0;
+            w[3] = w0_reciprocal(wt[0]);
+        }
+        mean[t] = ptf_mean_t ? ptf_mean_t[t] : a->ptf_mean;
+        CVQ_REQUIRE(std::isfinite(mean[t]), CVQ_ERR_INVALID, "ptf_mean must be finite" + at());
+        dynamic_pack(up.data(), t, cc.theta, cc.term1, cc.Ri, w);
+    }
+    if (mem == CVQ_MEM_DEVICE) return run_dynamic(p, *a, K, up.data(), levels, n_levels, var_out, es_out, m0_out);
+    const long long TL = T * n_levels;
+    int rc = ensure_io(p, 3 * TL);
+    if (rc) return rc;
+    CVQ_HIP_CHECK(hipSetDevice(p->device));
+    double* d_es = (es_out || m0_out) ? p->d_io + TL : nullptr;       // es is needed for m0's pass anyway
+    if ((rc = run_dynamic(p, *a, K, up.data(), levels, n_levels, p->d_io, d_es, m0_out ? p->d_io + 2 * TL : nullptr)))
+        return rc;
+    CVQ_HIP_CHECK(hipMemcpyAsync(var_out, p->d_io, TL * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    if (es_out)
+        CVQ_HIP_CHECK(hipMemcpyAsync(es_out, p->d_io + TL, TL * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    if (m0_out)
+        CVQ_HIP_CHECK(hipMemcpyAsync(m0_out, p->d_io + 2 * TL, TL * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    CVQ_HIP_CHECK(hipStreamSynchronize(p->stream));
+    return CVQ_OK;
+}
+
+int32_t cvq_dynamic_scratch(const cvq_plan* p, int32_t n_levels, int64_t* bytes) {
+    CVQ_REQUIRE(p != nullptr && bytes != nullptr, CVQ_ERR_INVALID, "NULL argument");
+    CVQ_REQUIRE(n_levels >= 1 && n_levels <= CVQ_MAX_LEVELS, CVQ_ERR_INVALID, "n_levels must be in [1, CVQ_MAX_LEVELS]");
+    CVQ_REQUIRE(p->T > 0, CVQ_ERR_STATE, "cvq_set_dates must be called first");
+    *bytes = (int64_t)(dynamic_scratch(p->S.dim, p->S.nrows, p->T, n_levels) * sizeof(double));
     return CVQ_OK;
 }
 

@@ -119,8 +119,9 @@ int32_t cvq_plan_info(const cvq_plan* plan, int64_t* reach_nodes, int32_t* rows)
  * live roofline).  kind: 0 tables, 1 joint-mass/prefix, 2 solve, 3 finalize,
  * 4 slab, 5 tail moments (cvq_slab_moments / cvq_expected_shortfall and the axis moments
  * cvq_slab_axis_moments / cvq_es_contributions: their tables,
- * partial sums and finish together), 6 exact quantiles (cvq_quantiles: its tables, passes
- * and updates together).  cvq_plan_timing(mask) times the kinds whose bit (1 << kind) is
+ * partial sums and finish together), 6 exact quantiles (cvq_quantiles and its conditional,
+ * batched-weights and per-date-record forms: their tables, passes and updates together).
+ * cvq_plan_timing(mask) times the kinds whose bit (1 << kind) is
  * set (0 = off, 0x7F = all) and clears previous records. */
 int32_t cvq_plan_timing(cvq_plan* plan, int32_t enable);
 int32_t cvq_plan_kernel_time(cvq_plan* plan, int32_t kind, double* total_ms, int32_t* launches);
@@ -311,6 +312,46 @@ int32_t cvq_portfolio_quantiles(cvq_plan* plan, const cvq_solve_args* args, cons
 /* Bytes of device scratch one cvq_portfolio_quantiles call of this shape takes on the plan's
  * current batch (a caller splitting a long candidate list sizes its calls with it). */
 int32_t cvq_portfolio_scratch(const cvq_plan* plan, int32_t n_portfolios, int32_t n_levels, int64_t* bytes);
+
+/* No reference counterpart.  cvq_quantiles under per-date copula parameters, weights and means on
+ * one plan: the exact quantile, Expected Shortfall and mass of a rolling backtest whose dependence
+ * is re-estimated (or follows a DCC-style path) and whose weights drift from date to date.
+ *   var / es / m0 [t][:] is what cvq_quantiles returns, bit for bit, on a plan that differs from
+ *   this one only in cvq_static.copula_params = copula_params_t[t], cvq_static.weights =
+ *   weights_t[t] and args->ptf_mean = ptf_mean_t[t], and that is given date t alone,
+ * cvq_plan_create's reciprocal rule included (weights_t[t][0] a power of two with a normal
+ * reciprocal: multiply by it; else divide).  copula_params_t follows cvq_static.copula_params'
+ * packing, [T][n_copula_params] with the plan's n_copula_params; weights_t [T][dim] follows
+ * cvq_static.weights' convention (Q10); ptf_mean_t [T].  A NULL array means the plan's own value
+ * (args->ptf_mean for the means) on every date; with all three NULL the call is cvq_quantiles, bit
+ * for bit, and args->ptf_mean is read only when ptf_mean_t is NULL.  Fixed per plan: the copula
+ * kind, the Gumbel survival flag and the Student nu (the t quantile tables and the integer-power
+ * paths hang on nu; copula_params_t[t][0] must repeat the plan's).
+ * A date's result depends on its own record and inputs alone: not on the other dates, their
+ * order or the number of levels, and it is bit-identical between runs (fixed-order sums; no
+ * atomics).  K, the bracket rule, the NaN convention outside the bracket and everything else are
+ * cvq_quantiles': runs on every strategy with no v_cap limit, on lazily sized scratch of its own
+ * (cvq_dynamic_scratch; a failed allocation is CVQ_ERR_OOM); the plan's solve state is untouched.
+ * The three per-date arrays and levels are host memory whatever `mem` says and need not outlive
+ * the call; var_out / es_out / m0_out [T][n_levels] host|device, the last two may be NULL.
+ * CVQ_MEM_DEVICE is stream-ordered without a host synchronisation.  Timed under kind 6.
+ * Everything is validated before any device work; a failure on a per-date value names the first
+ * offending date ("at date <t>") in cvq_last_error() and leaves the outputs unwritten:
+ *   CVQ_ERR_INVALID: NULL plan, args, levels or var_out; n_levels outside 1..CVQ_MAX_LEVELS; a
+ *     level <= 0 or NaN; max_var <= min_var; a non-finite parameter, weight or mean; Gumbel
+ *     theta < 1; Student nu <= 0; Gaussian / Student: a correlation with |rho| >= 1, or a matrix
+ *     whose cofactor determinant is not > 0 -- stricter than cvq_plan_create, which takes any
+ *     correlation values without this check;
+ *   CVQ_ERR_UNSUPPORTED: Gumbel theta > 16; weights_t[t][0] <= 0; a Student
+ *     copula_params_t[t][0] other than the plan's nu; K > 62;
+ *   CVQ_ERR_STATE: called before cvq_set_dates. */
+int32_t cvq_dynamic_quantiles(cvq_plan* plan, const cvq_solve_args* args, const double* copula_params_t,
+                              const double* weights_t, const double* ptf_mean_t, const double* levels,
+                              int32_t n_levels, double* var_out, double* es_out, double* m0_out, int32_t mem);
+
+/* Bytes of device scratch one cvq_dynamic_quantiles call of n_levels levels takes on the plan's
+ * current batch (the date records included). */
+int32_t cvq_dynamic_scratch(const cvq_plan* plan, int32_t n_levels, int64_t* bytes);
 
 /* Drop-in for ValueAtRiskCalcualtion.calc_var (calc_var_class.py:95-177 +
  * bisection_algorithm :250-309), quirks Q1-Q4 reproduced.  var_out [T];
