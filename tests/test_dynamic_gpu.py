@@ -5,7 +5,8 @@ plan, device mode, driver, CLI.  Inputs and checker results: tests/dynamic_cases
 The comparison with the checker is tests/test_portfolio_gpu.py's: margin >= 1e-7 asserted first
 (tests/test_dynamic_cpu.py holds the figures), then var with np.array_equal, m0 at the slab bar
 (rtol 1e-10, atol 1e-15) and |es - ref| <= 3e-10 (|m1 / m0| + |ptf_mean|).  Against a plan built
-with the date's parameters and weights, and between calls, everything is np.array_equal."""
+with the date's parameters and weights, and between calls, everything is np.array_equal.
+What the margin-1e-7 comparison cannot see (1e-8 of relative error in F, the narrow passes) is held by tests/test_quantile_probes_gpu.py."""
 import ctypes as C
 import functools
 
