@@ -27,12 +27,14 @@ CVQ_ERR_NUMERIC = -7
 
 MEM_HOST, MEM_DEVICE = 0, 1
 GAUSSIAN, STUDENT, PLACKETT, GUMBEL, GUMBEL_SURVIVAL = 0, 1, 2, 3, 4
+FRANK, JOE, JOE_SURVIVAL = 5, 6, 7
 MSM, GARCH, UKF = 0, 1, 2
 STRATEGY_PREFIX, STRATEGY_DIRECT, STRATEGY_COMPACT, STRATEGY_SORTED, STRATEGY_SWEEP = 0, 1, 2, 3, 4
 MAX_PORTFOLIOS = 64                   # CVQ_MAX_PORTFOLIOS: weight vectors per cvq_portfolio_quantiles call
 
 COPULA_KIND = {"gaussian": GAUSSIAN, "student": STUDENT, "plackett": PLACKETT,
-               "gumbel": GUMBEL, "gumbel_survival": GUMBEL_SURVIVAL}
+               "gumbel": GUMBEL, "gumbel_survival": GUMBEL_SURVIVAL,
+               "frank": FRANK, "joe": JOE, "joe_survival": JOE_SURVIVAL}
 MODEL_KIND = {"msm": MSM, "garch": GARCH, "mean_reverting": UKF, "ukf": UKF}
 
 _dp = C.POINTER(C.c_double)

@@ -101,3 +101,89 @@ def gumbel(cdf, theta, survival=False):
     """Pointwise Gumbel (survival=True: survival Gumbel) copula density, (P, d) -> (P,)."""
     with np.errstate(over="ignore", invalid="ignore"):
         return np.exp(gumbel_log_density(cdf, theta, survival))
+
+
+def _log1mexp(x):
+    """log(1 - e^-x) for x > 0: log1p(-exp(-x)) above log 2, log(-expm1(-x)) below."""
+    x = np.asarray(x, dtype=np.float64)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        return np.where(x > np.log(2.0), np.log1p(-np.exp(-x)), np.log(-np.expm1(-x)))
+
+
+def _product_form_log_density(a, B, p0, q0, kappa, c2, c3, lc):
+    """log c of a product-form Archimedean copula from the per-margin generator values a (P, d) and
+    log factors B (P, d): S = sum a, om = q0 - p0 expm1(-S) = 1 - p0 e^-S (a sum of
+    two non-negative terms), p = p0 e^-S,
+        log c = sum B + lc - S + (kappa - d) log om + log poly_d,
+        poly_2 = om + c2 p,  poly_3 = om^2 + p (c2 om + c3 p)."""
+    d = a.shape[1]
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore", under="ignore"):
+        S = np.sum(a, axis=1)
+        om = q0 - p0 * np.expm1(-S)
+        p = p0 * np.exp(-S)
+        poly = om + c2 * p if d == 2 else om * om + p * (c2 * om + c3 * p)
+        return np.sum(B, axis=1) + lc - S + (kappa - d) * np.log(om) + np.log(poly)
+
+
+def frank_log_density(cdf, theta):
+    """log c(u) of the exchangeable Frank copula
+        C(u) = -log(1 - prod_i (1 - e^(-theta u_i)) / (1 - e^-theta)^(d-1)) / theta,  theta > 0,
+    columns = assets (2 or 3).  Per margin, with g = 1 - e^-theta and X = e^-theta expm1(theta (1 - u)) / g:
+        a = -log((1 - e^(-theta u)) / g) = -log1p(-X)  (X <= 1/2) | log1mexp(theta) - log1mexp(theta u)
+        B = log theta - theta u + a - log1mexp(theta)
+    then the product form with p0 = g, q0 = e^-theta, kappa = 0, (c2, c3) = (1, 0) | (3, 2).
+    NaN where a u_i is not strictly inside (0, 1)."""
+    u = np.asarray(cdf, dtype=np.float64)
+    P, d = u.shape
+    if d not in (2, 3):
+        raise ValueError("the Frank copula is implemented for 2 or 3 marginals")
+    th = float(np.asarray(theta).reshape(-1)[0])
+    if not th > 0.0:
+        raise ValueError("the Frank copula is implemented for theta > 0")
+    g, lg = -np.expm1(-th), float(_log1mexp(th))
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        ok = np.all((u > 0.0) & (u < 1.0), axis=1)
+        X = np.exp(-th) * np.expm1(th * (1.0 - u)) / g
+        a = np.where(X <= 0.5, -np.log1p(-X), lg - _log1mexp(th * u))
+        B = np.log(th) - th * u + a - lg
+        c2, c3 = (1.0, 0.0) if d == 2 else (3.0, 2.0)
+        lc = _product_form_log_density(a, B, g, np.exp(-th), 0.0, c2, c3, lg - np.log(th))
+    return np.where(ok, lc, np.nan)
+
+
+def frank(cdf, theta):
+    """Pointwise Frank copula density, (P, d) -> (P,)."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        return np.exp(frank_log_density(cdf, theta))
+
+
+def joe_log_density(cdf, theta, survival=False):
+    """log c(u) of the exchangeable Joe copula C(u) = 1 - (1 - prod_i (1 - (1 - u_i)^theta))^(1/theta),
+    theta >= 1, columns = assets (2 or 3); survival: the 180-degree rotation c(1 - u).  Per margin,
+    with l = log1p(-u) (survival: log u):
+        a = -log1mexp(-theta l),  B = log theta + (theta - 1) l + a
+    then the product form with p0 = 1, q0 = 0, kappa = 1 / theta, k = 1 - kappa,
+    (c2, c3) = (k, 0) | (3 k, k (1 + k)).  NaN where a u_i is not strictly inside (0, 1)."""
+    u = np.asarray(cdf, dtype=np.float64)
+    P, d = u.shape
+    if d not in (2, 3):
+        raise ValueError("the Joe copula is implemented for 2 or 3 marginals")
+    th = float(np.asarray(theta).reshape(-1)[0])
+    if not th >= 1.0:
+        raise ValueError("the Joe copula is implemented for theta >= 1")
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        ok = np.all((u > 0.0) & (u < 1.0), axis=1)
+        ell = np.log(u) if survival else np.log1p(-u)
+        a = -_log1mexp(-th * ell)
+        B = np.log(th) + (th - 1.0) * ell + a
+        kap = 1.0 / th
+        k = 1.0 - kap
+        c2, c3 = (k, 0.0) if d == 2 else (3.0 * k, k * (1.0 + k))
+        lc = _product_form_log_density(a, B, 1.0, 0.0, kap, c2, c3, -np.log(th))
+    return np.where(ok, lc, np.nan)
+
+
+def joe(cdf, theta, survival=False):
+    """Pointwise Joe (survival=True: survival Joe) copula density, (P, d) -> (P,)."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        return np.exp(joe_log_density(cdf, theta, survival))

@@ -16,7 +16,7 @@ from scipy import special
 from scipy.optimize import minimize
 
 SIGMA_MODELS = ("garch", "mean_reverting", "ukf")
-COPULAS = ("gaussian", "student", "plackett", "gumbel", "gumbel_survival")
+COPULAS = ("gaussian", "student", "plackett", "gumbel", "gumbel_survival", "frank", "joe", "joe_survival")
 
 
 # ---------------------------------------------------------------------- weights
@@ -121,6 +121,14 @@ def fit_copula(copula: str, u, pdf, start=None, nu: Optional[float] = None, tppf
         return np.array([float(res["theta"])]), float(res["nll"])
     if copula in ("gumbel", "gumbel_survival"):
         opt = F.GumbelCopulaOptimizer(u, pdf, survival=copula == "gumbel_survival")
+        res = opt.optimize(theta_range=None if start is None else (float(np.asarray(start).reshape(-1)[0]),))
+        return np.array([float(res["theta"])]), float(res["nll"])
+    if copula == "frank":
+        opt = F.FrankCopulaOptimizer(u, pdf)
+        res = opt.optimize(theta_range=None if start is None else (float(np.asarray(start).reshape(-1)[0]),))
+        return np.array([float(res["theta"])]), float(res["nll"])
+    if copula in ("joe", "joe_survival"):
+        opt = F.JoeCopulaOptimizer(u, pdf, survival=copula == "joe_survival")
         res = opt.optimize(theta_range=None if start is None else (float(np.asarray(start).reshape(-1)[0]),))
         return np.array([float(res["theta"])]), float(res["nll"])
     raise ValueError(f"copula must be one of {COPULAS}")

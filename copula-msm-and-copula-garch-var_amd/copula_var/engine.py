@@ -37,7 +37,8 @@ PREFIX_MAX_N_3D = 64                  # PREFIX solves at most 4096 rows (cvq_pla
 PORTFOLIO_SCRATCH_BUDGET = 1 << 30    # bytes of device scratch one cvq_portfolio_quantiles call may take
                                       # (QuadraturePlan.portfolio_quantiles splits its candidates to stay below)
 MATERIALISED = ("prefix", "sorted", "sweep")   # strategies that hold only nodes with level <= v_cap
-SORTED_ONLY = ("gumbel", "gumbel_survival")     # copulas with SORTED instances only (cvq_plan_create)
+SORTED_ONLY = ("gumbel", "gumbel_survival", "frank", "joe", "joe_survival")   # copulas with SORTED instances
+                                      # only (cvq_plan_create)
 
 
 def general_power(copula: Optional[str], copula_params=None) -> bool:
@@ -53,7 +54,7 @@ def auto_strategy(model: str, dim: int, n: Optional[int] = None, copula: Optiona
                   copula_params=None) -> str:
     """The measured-fastest strategy per workload (cfg 1-5 on one MI355X)
     among those that run it, in the order the rule tests:
-      * the Gumbel copulas: SORTED, the only strategy with instances for them;
+      * the Gumbel, Frank and Joe copulas: SORTED, the only strategy with instances for them;
       * 2 assets, 512 < n <= 1024: SORTED, whose 1024-thread instance holds the grid (the
         reference takes any num_points, calc_var_class.py:16; main.py:50 suggests raising it);
       * 2 assets, a Student copula with a fitted (non-integer) nu: SORTED (cfg 2 10.7-11.0M vs
@@ -71,7 +72,7 @@ def auto_strategy(model: str, dim: int, n: Optional[int] = None, copula: Optiona
     COMPACT instances and n <= 512, else SORTED with v_cap at the grid's top)."""
     if copula in SORTED_ONLY:
         if dim not in SORTED_MAX_N:
-            raise ValueError(f"the Gumbel copulas run for 2 or 3 assets, got {dim}")
+            raise ValueError(f"the Gumbel, Frank and Joe copulas run for 2 or 3 assets, got {dim}")
         if n is not None and n > SORTED_MAX_N[dim]:
             raise ValueError(f"{dim}-asset grids support num_points <= {SORTED_MAX_N[dim]} (SORTED), got {n}")
         return "sorted"
@@ -161,7 +162,7 @@ class QuadraturePlan:
         """The plan that serves a query reaching level `top`: this one, or (strategy
         "auto" on a materialised strategy, top > v_cap) an unrestricted sibling --
         COMPACT in 2-D (its slabs run k_direct, any bounds), SORTED with v_cap at the grid's
-        top level in 3-D, for 2-D n > 512 and for the SORTED-only (Gumbel) copulas -- holding the
+        top level in 3-D, for 2-D n > 512 and for the SORTED-only (Gumbel, Frank, Joe) copulas -- holding the
         same per-date inputs."""
         if not self._auto or self.strategy not in MATERIALISED or not (top > self.v_cap):
             return self

@@ -52,7 +52,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--start", required=True)
     ap.add_argument("--end", default=None)
     ap.add_argument("--n-in", type=int, default=1135, help="in-sample days (main.py:34)")
-    ap.add_argument("--copula", default="student", choices=["student", "gaussian", "plackett", "gumbel", "gumbel_survival"])
+    ap.add_argument("--copula", default="student",
+                    choices=["student", "gaussian", "plackett", "gumbel", "gumbel_survival", "frank", "joe",
+                             "joe_survival"])
     ap.add_argument("--estimation", nargs="+", default=["garch", "msm"], choices=["garch", "msm", "mean_reverting"])
     ap.add_argument("--num-points", type=int, default=100)
     ap.add_argument("--k", type=int, default=4, help="MSM components")

@@ -19,7 +19,8 @@ from scipy.linalg import cholesky
 from scipy.optimize import minimize
 
 from .. import _native as N
-from ..copulas import gaussian_from_quantiles, gumbel_log_density, plackett, student_from_quantiles
+from ..copulas import (frank_log_density, gaussian_from_quantiles, gumbel_log_density, joe_log_density, plackett,
+                       student_from_quantiles)
 
 
 def construct_correlation_matrix(dim, corr_params):
@@ -236,3 +237,72 @@ class GumbelCopulaOptimizer(_IFM):
             raise ValueError("Gumbel copula fit: the negative log-likelihood is not finite at any start "
                              "(a NaN marginal, or a marginal density that is not positive)")
         return {"theta": best_theta, "nll": best_nll, "optimized_params": best_theta}
+
+
+class _OneParameterIFM(_IFM):
+    """IFM fit of a one-parameter copula by its closed-form log-density and a bounded 1-D search, as
+    GumbelCopulaOptimizer (whose note on saturated marginals applies unchanged: they are clamped
+    to [EDGE, 1 - EDGE], EDGE = 2^-53, and the row is kept)."""
+
+    NAME = ""
+    BOUNDS = (0.0, 1.0)
+    STARTS = ()
+    EDGE = 2.0 ** -53
+
+    def __init__(self, marginals, densities, tol=1e-9, max_iter=5000):
+        super().__init__(marginals, densities, tol, max_iter, device=0)
+        if self.dim not in (2, 3):
+            raise ValueError(f"the {self.NAME} copula is implemented for 2 or 3 marginals")
+        self._u = np.clip(self.marginals, self.EDGE, 1.0 - self.EDGE)      # NaN stays NaN
+
+    def _log_density(self, th):
+        raise NotImplementedError
+
+    def negative_log_likelihood(self, theta):
+        th = float(np.asarray(theta, dtype=np.float64).reshape(-1)[0])
+        total = self._log_dens + np.sum(self._log_density(th))
+        return -total if np.isfinite(total) else 1e10
+
+    def optimize(self, theta_range=None, method="L-BFGS-B"):
+        """One L-BFGS-B run per starting theta inside BOUNDS; the best NLL wins."""
+        if theta_range is None:
+            theta_range = self.STARTS
+        best_nll, best_theta = np.inf, None
+        for initial_theta in theta_range:
+            x0 = min(max(float(initial_theta), self.BOUNDS[0]), self.BOUNDS[1])
+            res = minimize(fun=self.negative_log_likelihood, x0=[x0], method=method,
+                           bounds=[self.BOUNDS], tol=self.tol, options={"maxiter": self.max_iter})
+            nll = self.negative_log_likelihood(res.x)
+            if nll < best_nll:
+                best_nll, best_theta = nll, float(res.x[0])
+        if best_theta is None or best_nll >= 1e10:
+            raise ValueError(f"{self.NAME} copula fit: the negative log-likelihood is not finite at any start "
+                             "(a NaN marginal, or a marginal density that is not positive)")
+        return {"theta": best_theta, "nll": best_nll, "optimized_params": best_theta}
+
+
+class FrankCopulaOptimizer(_OneParameterIFM):
+    """IFM fit of the Frank copula's theta (copulas.frank_log_density); dim 2 or 3."""
+
+    NAME = "Frank"
+    BOUNDS = (1e-3, 32.0)              # theta -> 0 is independence; the device plan takes theta <= 32
+    STARTS = (0.5, 2.0, 6.0, 15.0)
+
+    def _log_density(self, th):
+        return frank_log_density(self._u, th)
+
+
+class JoeCopulaOptimizer(_OneParameterIFM):
+    """IFM fit of the Joe (survival=True: survival Joe) copula's theta (copulas.joe_log_density);
+    dim 2 or 3."""
+
+    NAME = "Joe"
+    BOUNDS = (1.0001, 16.0)            # theta = 1 is independence; the device plan takes theta <= 16
+    STARTS = (1.2, 2.0, 4.0, 9.0)
+
+    def __init__(self, marginals, densities, survival=False, tol=1e-9, max_iter=5000):
+        super().__init__(marginals, densities, tol, max_iter)
+        self.survival = bool(survival)
+
+    def _log_density(self, th):
+        return joe_log_density(self._u, th, self.survival)

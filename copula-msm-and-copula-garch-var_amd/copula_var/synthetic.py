@@ -33,7 +33,7 @@ class Config:
     """One workload: model x copula x grid x dates (BASELINE.json ``configs``)."""
     name: str
     model: str                      # 'msm' | 'garch' | 'mean_reverting'
-    copula: str                     # 'gaussian' | 'student' | 'plackett' | 'gumbel' | 'gumbel_survival'
+    copula: str                     # 'gaussian' | 'student' | 'plackett' | 'gumbel[_survival]' | 'frank' | 'joe[_survival]'
     dim: int
     num_points: int
     T: int
@@ -65,7 +65,7 @@ class Config:
         if self.copula == "gaussian":
             iu = np.triu_indices(self.dim, k=1)
             return np.asarray(self.corr, dtype=np.float64)[iu].copy()
-        if self.copula in ("plackett", "gumbel", "gumbel_survival"):
+        if self.copula in ("plackett", "gumbel", "gumbel_survival", "frank", "joe", "joe_survival"):
             return float(self.theta)
         raise ValueError(f"unknown copula {self.copula}")
 

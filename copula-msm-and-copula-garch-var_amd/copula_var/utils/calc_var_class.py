@@ -34,7 +34,7 @@ from ..engine import QuadraturePlan
 
 
 DEVICE_MODELS = ("msm", "garch", "mean_reverting")
-DEVICE_COPULAS = ("student", "gaussian", "plackett", "gumbel", "gumbel_survival")
+DEVICE_COPULAS = ("student", "gaussian", "plackett", "gumbel", "gumbel_survival", "frank", "joe", "joe_survival")
 
 
 def check_device_adapter(method) -> None:

@@ -1,6 +1,7 @@
 """(copula x model) factory -- utils/factory.py:10-31 of the reference, including
 Q17: ('mean_reverting', 'gaussian') maps to the Plackett adapter (factory.py:22-23).
-The Gumbel rows have no reference counterpart."""
+The Gumbel, Frank and Joe rows have no reference counterpart."""
+from .model_estimation.copula.archimedean_estimation import FrankCopulaVaR, JoeCopulaVaR, JoeSurvivalCopulaVaR
 from .model_estimation.copula.gaussian_estimation import GaussianCopulaVaR
 from .model_estimation.copula.gumbel_estimation import GumbelCopulaVaR, GumbelSurvivalCopulaVaR
 from .model_estimation.copula.plackett_estimation import PlackettCopulaVaR
@@ -25,6 +26,15 @@ _TABLE = {
     ("msm", "gumbel_survival"): (GumbelSurvivalCopulaVaR, MSMEstimation),
     ("garch", "gumbel_survival"): (GumbelSurvivalCopulaVaR, GarchEstimation),
     ("mean_reverting", "gumbel_survival"): (GumbelSurvivalCopulaVaR, MeanRevertingEstimation),
+    ("msm", "frank"): (FrankCopulaVaR, MSMEstimation),
+    ("garch", "frank"): (FrankCopulaVaR, GarchEstimation),
+    ("mean_reverting", "frank"): (FrankCopulaVaR, MeanRevertingEstimation),
+    ("msm", "joe"): (JoeCopulaVaR, MSMEstimation),
+    ("garch", "joe"): (JoeCopulaVaR, GarchEstimation),
+    ("mean_reverting", "joe"): (JoeCopulaVaR, MeanRevertingEstimation),
+    ("msm", "joe_survival"): (JoeSurvivalCopulaVaR, MSMEstimation),
+    ("garch", "joe_survival"): (JoeSurvivalCopulaVaR, GarchEstimation),
+    ("mean_reverting", "joe_survival"): (JoeSurvivalCopulaVaR, MeanRevertingEstimation),
 }
 
 

@@ -97,6 +97,7 @@ int launch_attrib(const StaticDev& S, long long T, hipStream_t stream, const dou
         case CVQ_STUDENT: attrib_cop<CVQ_STUDENT>(L); break;
         case CVQ_PLACKETT: attrib_cop<CVQ_PLACKETT>(L); break;
         case CVQ_GUMBEL: attrib_cop<CVQ_GUMBEL>(L); break;
+        case CVQ_PRODFORM: attrib_cop<CVQ_PRODFORM>(L); break;
         default: CVQ_REQUIRE(false, CVQ_ERR_INVALID, "unknown copula kind");
     }
     CVQ_HIP_CHECK(hipGetLastError());

@@ -22,7 +22,8 @@ struct StaticDev {
     double node_ex;               // -(nu+dim)/2
     double uni_ex;                // -(nu+1)/2
     int uni_m;                    // 2 * (nu+1)/2 when a half-integer <= 16, else -1
-    int survival;                 // Gumbel: the margins are rotated (1 - u); read where tables are built
+    int survival;                 // family code of the log-B kinds (kFam*): bit 0 = the margins are rotated
+                                  // (1 - u), bits 1.. = the family; read where tables and nodes are built
     double term1;                 // multivariate density constant (student.py:138 / gaussian.py:107)
     double g_uni;                 // univariate t constant (student.py:164)
     double inv_g_uni;             // 1 / g_uni (the integer-nu table path multiplies)
@@ -39,6 +40,12 @@ struct StaticDev {
     const long long* off;         // [nrows] row offset into a date's prefix block
     long long G;                  // reachable nodes per date (sum kmax)
 };
+
+// StaticDev::survival of the log-B kernel kinds.  CVQ_GUMBEL's instances serve both Gumbel kinds
+// (codes 0 / 1, a plain rotation flag); CVQ_FRANK's -- the product-form kind -- serve Frank and both
+// Joe kinds.
+constexpr int kFamGumbel = 0, kFamGumbelSurvival = 1, kFamFrank = 2, kFamJoe = 4, kFamJoeSurvival = 5;
+constexpr int CVQ_PRODFORM = CVQ_FRANK;          // kernel kind of Frank, Joe and survival Joe
 
 // Integer code of a half-integer power b^(+-m/2): m when m is an integer in [0, limit], else -1
 // (the general power exp(ex log b)).  The plan's node_m = half_power_code(nu + dim, 128) and
@@ -86,7 +93,7 @@ struct alignas(16) Header {       // per-rank solve summary, all-gathered across
 // Layout key of the structs passed between translation units (cvq_plan.hip launches the
 // kernels compiled in cvq_compact.hip / cvq_sorted.hip): a stale object fails its launch
 // with CVQ_ERR_STATE instead of reading misplaced pointers.
-constexpr size_t kAbiVersion = 7;
+constexpr size_t kAbiVersion = 8;
 __host__ __device__ constexpr size_t kernel_abi_key() {
     return kAbiVersion * 1000003u + sizeof(StaticDev) * 4099u + sizeof(SolveConst) * 67u + sizeof(Header);
 }

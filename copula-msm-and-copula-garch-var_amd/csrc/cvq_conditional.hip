@@ -84,6 +84,7 @@ void cond_pass(const CondLaunch& L) {
         case CVQ_STUDENT: cond_cop<CVQ_STUDENT, C>(L); break;
         case CVQ_PLACKETT: cond_cop<CVQ_PLACKETT, C>(L); break;
         case CVQ_GUMBEL: cond_cop<CVQ_GUMBEL, C>(L); break;
+        case CVQ_PRODFORM: cond_cop<CVQ_PRODFORM, C>(L); break;
         default: break;                                // launch_conditional rejects unknown kinds
     }
 }
@@ -133,6 +134,7 @@ int launch_conditional(const StaticDev& S, long long T, hipStream_t stream, cons
         case CVQ_STUDENT: if (msm) cond_tables<CVQ_STUDENT, true>(Q); else cond_tables<CVQ_STUDENT, false>(Q); break;
         case CVQ_PLACKETT: if (msm) cond_tables<CVQ_PLACKETT, true>(Q); else cond_tables<CVQ_PLACKETT, false>(Q); break;
         case CVQ_GUMBEL: if (msm) cond_tables<CVQ_GUMBEL, true>(Q); else cond_tables<CVQ_GUMBEL, false>(Q); break;
+        case CVQ_PRODFORM: if (msm) cond_tables<CVQ_PRODFORM, true>(Q); else cond_tables<CVQ_PRODFORM, false>(Q); break;
         default: CVQ_REQUIRE(false, CVQ_ERR_INVALID, "unknown copula kind");
     }
     CVQ_HIP_CHECK(hipGetLastError());

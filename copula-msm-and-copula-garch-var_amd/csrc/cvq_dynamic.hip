@@ -81,6 +81,7 @@ void dyn_pass(const DynLaunch& L) {
         case CVQ_STUDENT: dyn_cop<CVQ_STUDENT, C>(L); break;
         case CVQ_PLACKETT: dyn_cop<CVQ_PLACKETT, C>(L); break;
         case CVQ_GUMBEL: dyn_cop<CVQ_GUMBEL, C>(L); break;
+        case CVQ_PRODFORM: dyn_cop<CVQ_PRODFORM, C>(L); break;
         default: break;                                // launch_dynamic rejects unknown kinds
     }
 }
@@ -146,6 +147,7 @@ int launch_dynamic(const StaticDev& S, long long T, hipStream_t stream, const do
         case CVQ_STUDENT: if (msm) dyn_tables<CVQ_STUDENT, true>(Q); else dyn_tables<CVQ_STUDENT, false>(Q); break;
         case CVQ_PLACKETT: if (msm) dyn_tables<CVQ_PLACKETT, true>(Q); else dyn_tables<CVQ_PLACKETT, false>(Q); break;
         case CVQ_GUMBEL: if (msm) dyn_tables<CVQ_GUMBEL, true>(Q); else dyn_tables<CVQ_GUMBEL, false>(Q); break;
+        case CVQ_PRODFORM: if (msm) dyn_tables<CVQ_PRODFORM, true>(Q); else dyn_tables<CVQ_PRODFORM, false>(Q); break;
         default: CVQ_REQUIRE(false, CVQ_ERR_INVALID, "unknown copula kind");
     }
     CVQ_HIP_CHECK(hipGetLastError());

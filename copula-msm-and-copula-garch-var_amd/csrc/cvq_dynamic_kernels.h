@@ -46,7 +46,8 @@ __device__ __forceinline__ void dyn_overlay(StaticDev& S, const double* __restri
     S.w0_inv = rec[kDynW0Inv];
 }
 
-// k_moments_tables with the date's theta (Gumbel: A = x^theta, B's (theta - 1) log x); the other
+// k_moments_tables with the date's theta (Gumbel: A = x^theta, B's (theta - 1) log x; Frank / Joe:
+// prod_entry's generator value and log factor); the other
 // kinds' tables do not depend on the varying parameters and never read the records.
 template <int COP, bool MSM, bool TAB>
 __global__ __launch_bounds__(256) void k_dyn_tables(StaticDev S0, long long T, const double* __restrict__ a,
@@ -58,7 +59,7 @@ __global__ __launch_bounds__(256) void k_dyn_tables(StaticDev S0, long long T, c
     const long long td = idx / S0.n;
     const int d = (int)(td % S0.dim);
     double A, B;
-    if constexpr (COP == CVQ_GUMBEL) {
+    if constexpr (kLogB<COP>) {
         StaticDev S = S0;
         S.theta = rec[(td / S0.dim) * kDynRec + kDynTheta];
         table_entry<COP, MSM, TAB>(S, a, td, d, i, &A, &B);

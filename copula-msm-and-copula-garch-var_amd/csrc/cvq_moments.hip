@@ -92,6 +92,7 @@ int launch_moments(const StaticDev& S, long long T, hipStream_t stream, const do
         case CVQ_STUDENT: moments_cop<CVQ_STUDENT>(L); break;
         case CVQ_PLACKETT: moments_cop<CVQ_PLACKETT>(L); break;
         case CVQ_GUMBEL: moments_cop<CVQ_GUMBEL>(L); break;
+        case CVQ_PRODFORM: moments_cop<CVQ_PRODFORM>(L); break;
         default: CVQ_REQUIRE(false, CVQ_ERR_INVALID, "unknown copula kind");
     }
     CVQ_HIP_CHECK(hipGetLastError());

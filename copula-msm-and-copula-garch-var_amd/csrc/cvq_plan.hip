@@ -382,7 +382,7 @@ int launch_direct(cvq_plan* p, const SolveConst& P, int mode, const double* boun
         case CVQ_GAUSSIAN: launch_direct_c<CVQ_GAUSSIAN>(p, P, mode, bounds, out, snaps, hdr); break;
         case CVQ_STUDENT: launch_direct_c<CVQ_STUDENT>(p, P, mode, bounds, out, snaps, hdr); break;
         case CVQ_PLACKETT: launch_direct_c<CVQ_PLACKETT>(p, P, mode, bounds, out, snaps, hdr); break;
-        default: CVQ_REQUIRE(false, CVQ_ERR_UNSUPPORTED, "the Gumbel copulas run on the SORTED strategy");
+        default: CVQ_REQUIRE(false, CVQ_ERR_UNSUPPORTED, "the Gumbel, Frank and Joe copulas run on the SORTED strategy");
     }
     CVQ_HIP_CHECK(hipGetLastError());
     return CVQ_OK;
@@ -1084,7 +1084,7 @@ int dispatch_cop(cvq_plan* p, bool tables) {
         case CVQ_STUDENT: launch_cop<CVQ_STUDENT>(p, tables); break;
         case CVQ_PLACKETT: launch_cop<CVQ_PLACKETT>(p, tables); break;
         // SORTED evaluates the Gumbel tables itself (direct_fused); no k_tables / k_mass instances
-        default: CVQ_REQUIRE(false, CVQ_ERR_UNSUPPORTED, "the Gumbel copulas run on the SORTED strategy");
+        default: CVQ_REQUIRE(false, CVQ_ERR_UNSUPPORTED, "the Gumbel, Frank and Joe copulas run on the SORTED strategy");
     }
     CVQ_HIP_CHECK(hipGetLastError());
     return CVQ_OK;
@@ -1310,7 +1310,7 @@ double invert(const double* R, int d, double* Ri) {
 
 // The copula constants of the generic node path, computed as the reference does on the host, for
 // one parameter vector cp (cvq_static.copula_params' packing; nu = cp[0] of a Student copula):
-// theta (Plackett, Gumbel), or the inverse correlation Ri and the density constant term1 (Gaussian,
+// theta (Plackett, Gumbel, Frank, Joe), or the inverse correlation Ri and the density constant term1 (Gaussian,
 // Student).  cvq_plan_create and cvq_dynamic_quantiles both take them from here, so a date's record
 // holds the bits a plan created with that date's parameters would.  Returns invert()'s determinant
 // (1 for the kinds without a correlation matrix).
@@ -1319,7 +1319,7 @@ struct CopulaConst {
     double Ri[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 };
 double copula_constants(int copula, int d, const double* cp, CopulaConst* out) {
-    if (copula == CVQ_PLACKETT || copula == CVQ_GUMBEL || copula == CVQ_GUMBEL_SURVIVAL) {
+    if (copula == CVQ_PLACKETT || (copula >= CVQ_GUMBEL && copula <= CVQ_JOE_SURVIVAL)) {
         out->theta = cp[0];
         return 1.0;
     }
@@ -1402,7 +1402,7 @@ int run_dynamic(cvq_plan* p, const cvq_solve_args& a, int K, const double* up, c
 extern "C" {
 
 const char* cvq_last_error(void) { return g_err.c_str(); }
-int32_t cvq_version(void) { return 10800; }
+int32_t cvq_version(void) { return 10900; }
 
 int32_t cvq_device_count(int32_t* count) {
     CVQ_REQUIRE(count != nullptr, CVQ_ERR_INVALID, "count is NULL");
@@ -1418,8 +1418,9 @@ int32_t cvq_plan_create(const cvq_static* s, int32_t device, cvq_plan** out) {
     CVQ_REQUIRE(s != nullptr && out != nullptr, CVQ_ERR_INVALID, "NULL argument");
     *out = nullptr;
     CVQ_REQUIRE(s->model >= CVQ_MSM && s->model <= CVQ_UKF, CVQ_ERR_INVALID, "unknown model kind");
-    CVQ_REQUIRE(s->copula >= CVQ_GAUSSIAN && s->copula <= CVQ_GUMBEL_SURVIVAL, CVQ_ERR_INVALID, "unknown copula kind");
+    CVQ_REQUIRE(s->copula >= CVQ_GAUSSIAN && s->copula <= CVQ_JOE_SURVIVAL, CVQ_ERR_INVALID, "unknown copula kind");
     const bool gumbel = s->copula == CVQ_GUMBEL || s->copula == CVQ_GUMBEL_SURVIVAL;
+    const bool frank = s->copula == CVQ_FRANK, joe = s->copula == CVQ_JOE || s->copula == CVQ_JOE_SURVIVAL;
     CVQ_REQUIRE(s->dim == 2 || s->dim == 3, CVQ_ERR_UNSUPPORTED, "dim must be 2 or 3");
     CVQ_REQUIRE(!(s->copula == CVQ_PLACKETT && s->dim != 2), CVQ_ERR_UNSUPPORTED,
                 "Plackett copula is only defined for 2-dimensional marginals (plackett.py:20-21)");
@@ -1452,6 +1453,25 @@ int32_t cvq_plan_create(const cvq_static* s, int32_t device, cvq_plan** out) {
         CVQ_REQUIRE(s->strategy == CVQ_STRATEGY_SORTED, CVQ_ERR_UNSUPPORTED,
                     "the Gumbel copulas run on the SORTED strategy (CVQ_STRATEGY_SORTED) only");
     }
+    if (frank) {
+        CVQ_REQUIRE(s->n_copula_params == 1, CVQ_ERR_INVALID, "the Frank copula takes one parameter (theta)");
+        const double th = s->copula_params[0];
+        CVQ_REQUIRE(th == th && th != 0.0, CVQ_ERR_INVALID, "Frank theta must be > 0 (theta = 0 is independence)");
+        CVQ_REQUIRE(th > 0.0, CVQ_ERR_UNSUPPORTED, "Frank theta < 0 (negative dependence) is not supported");
+        CVQ_REQUIRE(th <= 32.0, CVQ_ERR_UNSUPPORTED,
+                    "Frank theta must be <= 32 (Kendall tau 0.88): beyond it e^-theta is lost against 1");
+        CVQ_REQUIRE(s->strategy == CVQ_STRATEGY_SORTED, CVQ_ERR_UNSUPPORTED,
+                    "the Frank copula runs on the SORTED strategy (CVQ_STRATEGY_SORTED) only");
+    }
+    if (joe) {
+        CVQ_REQUIRE(s->n_copula_params == 1, CVQ_ERR_INVALID, "the Joe copulas take one parameter (theta)");
+        const double th = s->copula_params[0];
+        CVQ_REQUIRE(th == th && th >= 1.0, CVQ_ERR_INVALID, "Joe theta must be >= 1");
+        CVQ_REQUIRE(th <= 16.0, CVQ_ERR_UNSUPPORTED,
+                    "Joe theta must be <= 16 (Kendall tau 0.89): beyond it (1 - u)^theta leaves double range at the grid edges");
+        CVQ_REQUIRE(s->strategy == CVQ_STRATEGY_SORTED, CVQ_ERR_UNSUPPORTED,
+                    "the Joe copulas run on the SORTED strategy (CVQ_STRATEGY_SORTED) only");
+    }
     for (int l = 0; l < Q; ++l) {             // create_vol_combinations ij order (msm_estimation.py:384)
         int rem = l;
         for (int d = s->dim - 1; d >= 0; --d) {
@@ -1472,8 +1492,10 @@ int32_t cvq_plan_create(const cvq_static* s, int32_t device, cvq_plan** out) {
     p->hx.assign(s->x_values, s->x_values + s->n);
     StaticDev& S = p->S;
     S.model = s->model;
-    S.copula = gumbel ? CVQ_GUMBEL : s->copula;    // one kernel kind; survival only rotates the margins
-    S.survival = s->copula == CVQ_GUMBEL_SURVIVAL ? 1 : 0;
+    // one kernel kind per family shape; the family code tells the kinds of one shape apart
+    S.copula = gumbel ? CVQ_GUMBEL : (frank || joe) ? CVQ_PRODFORM : s->copula;
+    S.survival = s->copula == CVQ_GUMBEL_SURVIVAL ? kFamGumbelSurvival : frank ? kFamFrank
+               : s->copula == CVQ_JOE ? kFamJoe : s->copula == CVQ_JOE_SURVIVAL ? kFamJoeSurvival : kFamGumbel;
     S.dim = s->dim;
     S.n = s->n;
     S.q = s->q;
@@ -1494,7 +1516,7 @@ int32_t cvq_plan_create(const cvq_static* s, int32_t device, cvq_plan** out) {
     p->n_cp = s->n_copula_params;
     if (s->copula == CVQ_PLACKETT) {
         CVQ_REQUIRE(s->n_copula_params >= 1, CVQ_ERR_INVALID, "Plackett needs theta");
-    } else if (!gumbel) {
+    } else if (!gumbel && !frank && !joe) {
         const int nrho = d * (d - 1) / 2;
         const int base = s->copula == CVQ_STUDENT ? 1 : 0;
         CVQ_REQUIRE(s->n_copula_params == base + nrho, CVQ_ERR_INVALID, "wrong copula parameter count");
@@ -2095,7 +2117,10 @@ int32_t cvq_dynamic_quantiles(cvq_plan* p, const cvq_solve_args* a, const double
     const StaticDev& S = p->S;
     const long long T = p->T;
     const int d = S.dim, ncp = p->n_cp;
-    const int kind = S.copula == CVQ_GUMBEL && S.survival ? CVQ_GUMBEL_SURVIVAL : S.copula;
+    const int kind = S.copula == CVQ_GUMBEL ? (S.survival ? CVQ_GUMBEL_SURVIVAL : CVQ_GUMBEL)
+                   : S.copula == CVQ_PRODFORM ? (S.survival == kFamFrank ? CVQ_FRANK
+                                                 : S.survival == kFamJoe ? CVQ_JOE : CVQ_JOE_SURVIVAL)
+                                              : S.copula;
     // the date records, each formed as cvq_plan_create forms the plan's own constants
     std::vector<double> up(dynamic_upload_doubles(T));
     double* mean = up.data() + dynamic_mean_offset(T);
@@ -2113,6 +2138,15 @@ int32_t cvq_dynamic_quantiles(cvq_plan* p, const cvq_solve_args* a, const double
             if (S.copula == CVQ_GUMBEL) {
                 CVQ_REQUIRE(cp[0] >= 1.0, CVQ_ERR_INVALID, "Gumbel theta must be >= 1" + at());
                 CVQ_REQUIRE(cp[0] <= 16.0, CVQ_ERR_UNSUPPORTED, "Gumbel theta must be <= 16" + at());
+            }
+            if (kind == CVQ_FRANK) {
+                CVQ_REQUIRE(cp[0] != 0.0, CVQ_ERR_INVALID, "Frank theta must be > 0" + at());
+                CVQ_REQUIRE(cp[0] > 0.0, CVQ_ERR_UNSUPPORTED, "Frank theta < 0 is not supported" + at());
+                CVQ_REQUIRE(cp[0] <= 32.0, CVQ_ERR_UNSUPPORTED, "Frank theta must be <= 32" + at());
+            }
+            if (kind == CVQ_JOE || kind == CVQ_JOE_SURVIVAL) {
+                CVQ_REQUIRE(cp[0] >= 1.0, CVQ_ERR_INVALID, "Joe theta must be >= 1" + at());
+                CVQ_REQUIRE(cp[0] <= 16.0, CVQ_ERR_UNSUPPORTED, "Joe theta must be <= 16" + at());
             }
             if (S.copula == CVQ_STUDENT) {
                 CVQ_REQUIRE(cp[0] > 0.0, CVQ_ERR_INVALID, "nu must be > 0" + at());

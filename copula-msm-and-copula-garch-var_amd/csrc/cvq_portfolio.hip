@@ -89,6 +89,7 @@ void port_pass(const PortLaunch& L) {
         case CVQ_STUDENT: port_cop<CVQ_STUDENT, C>(L); break;
         case CVQ_PLACKETT: port_cop<CVQ_PLACKETT, C>(L); break;
         case CVQ_GUMBEL: port_cop<CVQ_GUMBEL, C>(L); break;
+        case CVQ_PRODFORM: port_cop<CVQ_PRODFORM, C>(L); break;
         default: break;                                // launch_portfolios rejects unknown kinds
     }
 }
@@ -149,6 +150,7 @@ int launch_portfolios(const StaticDev& S, long long T, hipStream_t stream, const
         case CVQ_STUDENT: if (msm) port_tables<CVQ_STUDENT, true>(Q); else port_tables<CVQ_STUDENT, false>(Q); break;
         case CVQ_PLACKETT: if (msm) port_tables<CVQ_PLACKETT, true>(Q); else port_tables<CVQ_PLACKETT, false>(Q); break;
         case CVQ_GUMBEL: if (msm) port_tables<CVQ_GUMBEL, true>(Q); else port_tables<CVQ_GUMBEL, false>(Q); break;
+        case CVQ_PRODFORM: if (msm) port_tables<CVQ_PRODFORM, true>(Q); else port_tables<CVQ_PRODFORM, false>(Q); break;
         default: CVQ_REQUIRE(false, CVQ_ERR_INVALID, "unknown copula kind");
     }
     CVQ_HIP_CHECK(hipGetLastError());

@@ -70,6 +70,7 @@ __global__ void k_phi(StaticDev S, const double* __restrict__ uvs, double* __res
 //   A   = z = t.ppf(u, nu) | norm.ppf(u)        (Plackett: A = u)
 //   B   = pdf / univariate-copula-margin-pdf      (MSM: pdf = 1; Plackett: B = pdf)
 //   Gumbel: A = (-log u)^theta, B = log(pdf (-log u)^(theta-1) / u), with 1 - u for u under survival
+//   Frank / Joe (product form): A = the generator value a(u) >= 0, B = log(-a'(u) pdf) + a (prod_entry)
 // Layout [T][dim][n], coalesced along i.
 // TAB: the plan has verified direct t.ppf tables (Student only; see stdtrit_tabulated).
 // Marginal CDF value u and density factor of grid index i on axis d, date row td.
@@ -111,6 +112,96 @@ __device__ __forceinline__ void marginal_u(const StaticDev& S, const double* __r
 constexpr double kGumbelFloor = 1.0e-300;            // floor of a Gumbel table entry x^theta (table_entry)
 constexpr double kLog2e = 1.4426950408889634;
 
+// Kinds whose B table is a LOG factor (outer_B adds, make_row keeps no quadratic form): the Gumbel
+// kind and the product-form kind (Frank, Joe, survival Joe)
+template <int COP>
+constexpr bool kLogB = COP == CVQ_GUMBEL || COP == CVQ_PRODFORM;
+
+// log(1 - e^-x), x > 0
+__device__ __forceinline__ double log1mexp(double x) {
+    return x > 0.6931471805599453 ? log1p(-exp(-x)) : log(-expm1(-x));
+}
+
+// Product-form Archimedean kinds.  With the generator values a_i >= 0 of the axes and
+// S = sum a_i, E = expm1(-S), om = q0 - p0 E (= 1 - p0 e^-S, formed without cancellation: both terms
+// are >= 0) and p = p0 e^-S:
+//   log(c prod pdf) = sum B_i + lc - S + (kappa - d) log om + log poly_d(om, p)
+//   poly_2 = om + c2 p,   poly_3 = om^2 + p (c2 om + c3 p)
+// i.e. (kappa - 1) log om + log(1 + y (c2 + c3 y)), y = p / om, multiplied through by om^(d-1): no
+// division, and no y^2 that leaves double range where every a_i sits at the tables' floor.
+//   Frank: p0 = g = 1 - e^-theta, q0 = e^-theta, kappa = 0, (c2, c3) = (1, 0) | (3, 2)
+//   Joe:   p0 = 1, q0 = 0, kappa = 1 / theta, k = 1 - kappa, (c2, c3) = (k, 0) | (3 k, k (1 + k))
+// lc = log p0 - log theta.  One function derives them from (family code, theta), so a plan's theta
+// and a date record's (dyn_overlay) give the same bits.
+struct ProdConst {
+    double p0, q0, e, c2, c3, lc;                  // e = kappa - d
+};
+__device__ __forceinline__ ProdConst prod_const(int fam, double th, int dim) {
+    ProdConst c;
+    if (fam == kFamFrank) {
+        c.p0 = -expm1(-th);
+        c.q0 = exp(-th);
+        c.e = -(double)dim;
+        c.c2 = dim == 2 ? 1.0 : 3.0;
+        c.c3 = dim == 2 ? 0.0 : 2.0;
+        c.lc = log1mexp(th) - log(th);
+    } else {
+        const double kap = 1.0 / th, k = 1.0 - kap;
+        c.p0 = 1.0;
+        c.q0 = 0.0;
+        c.e = kap - (double)dim;
+        c.c2 = dim == 2 ? k : 3.0 * k;
+        c.c3 = dim == 2 ? 0.0 : k * (1.0 + k);
+        c.lc = -log(th);
+    }
+    return c;
+}
+
+// (a, B) of one table entry, u strictly inside (0, 1):
+//   Frank: X = e^-theta expm1(theta (1 - u)) / g = 1 - (1 - e^(-theta u)) / g,
+//          a = -log1p(-X) (X <= 1/2) | log1mexp(theta) - log1mexp(theta u): accurate at both ends
+//          B = log theta - theta u + a - log1mexp(theta) + log pdf
+//   Joe:   l = log1p(-u) (survival: log u), a = -log1mexp(-theta l), B = log theta + (theta - 1) l + a + log pdf
+__device__ __forceinline__ void prod_entry(int fam, double th, double u, double pdf, double* a_out, double* B_out) {
+    double a, B;
+    if (fam == kFamFrank) {
+        const double g = -expm1(-th), lg = log1mexp(th);
+        const double X = exp(-th) * expm1(th * (1.0 - u)) / g;
+        a = X <= 0.5 ? -log1p(-X) : lg - log1mexp(th * u);
+        B = ((log(th) - th * u) + a) - lg;
+    } else {
+        const double l = (fam & 1) ? log(u) : log1p(-u);
+        a = -log1mexp(-th * l);
+        B = (log(th) + (th - 1.0) * l) + a;
+    }
+    *a_out = a;
+    *B_out = B + log(pdf);
+}
+
+// expm1(-s) for s >= 0 without branches, and e^-s: the Taylor series of (e^x - 1) / x to x^13 below
+// s = 1/2 (truncation 5e-17 relative), exp_node - 1 above (its 1.4e-14 relative to e^-s is at most
+// 2.2e-14 relative to 1 - e^-s there).  s = +inf or NaN gives NaN.
+__device__ __forceinline__ double expm1_neg_node(double s, double* ex_out) {
+    const double x = -s;
+    const double ex = exp_node(x);
+    double p = 1.1470745597729725e-11;             // 1 / 14!
+    p = fma(p, x, 1.6059043836821613e-10);         // 1 / 13!
+    p = fma(p, x, 2.08767569878681e-09);
+    p = fma(p, x, 2.505210838544172e-08);
+    p = fma(p, x, 2.755731922398589e-07);
+    p = fma(p, x, 2.7557319223985893e-06);
+    p = fma(p, x, 2.48015873015873e-05);
+    p = fma(p, x, 0.0001984126984126984);
+    p = fma(p, x, 0.001388888888888889);
+    p = fma(p, x, 0.008333333333333333);
+    p = fma(p, x, 0.041666666666666664);
+    p = fma(p, x, 0.16666666666666666);
+    p = fma(p, x, 0.5);
+    p = fma(p, x, 1.0);
+    *ex_out = ex;
+    return s < 0.5 ? x * p : ex - 1.0;
+}
+
 // NUI > 0 (with TAB): the Student nu is the integer NUI -- quantile tail variable by root_nu,
 // B = pdf (1 + z^2/nu)^((nu+1)/2) / g_uni without divisions (~1 ulp from the reference's
 // arithmetic; the VaR tolerates ~1e-8 relative node noise)
@@ -137,6 +228,14 @@ __device__ __forceinline__ void table_entry(const StaticDev& S, const double* __
         const double lx = log(-l);
         *A_out = live ? fmax(exp(S.theta * lx), kGumbelFloor) : __builtin_nan("");
         *B_out = live ? (log(pdf) + (S.theta - 1.0) * lx) - l : 0.0;
+    } else if constexpr (COP == CVQ_PRODFORM) {
+        // generator value a, floored at kGumbelFloor (S = sum a stays normal: a floored entry only
+        // lowers the node), and the log factor B; dead entries as the Gumbel kind's
+        const bool live = u > 0.0 && u < 1.0;
+        double av, Bv;
+        prod_entry(S.survival, S.theta, u, pdf, &av, &Bv);
+        *A_out = live ? fmax(av, kGumbelFloor) : __builtin_nan("");
+        *B_out = live ? Bv : 0.0;
     } else if (COP == CVQ_PLACKETT) {
         *A_out = u;
         *B_out = pdf;
@@ -202,6 +301,18 @@ __device__ __forceinline__ double node_value(const StaticDev& S, const RowCtx& r
         const double poly = DIM == 2 ? Av + t1 : fma(Av, fma(3.0, t1, Av), t1 * (2.0 * th - 1.0));
         const double v = (exp_node(fma(1.0 - DIM * th, lA, (r.B + Bc) - Av)) * poly) * W;
         return isfinite(v) ? v : 0.0;
+    } else if constexpr (COP == CVQ_PRODFORM) {
+        // (prod_const) Gumbel's dead rule: a NaN table entry or a non-finite value is a node of 0
+        const ProdConst pc = prod_const(S.survival, S.theta, DIM);
+        const double Sx = (DIM == 2 ? r.z0 : r.z0 + r.z1) + zc;
+        if (!(Sx == Sx)) return 0.0;
+        double ex;
+        const double E = expm1_neg_node(Sx, &ex);
+        const double om = fma(-pc.p0, E, pc.q0);
+        const double p = pc.p0 * ex;
+        const double poly = DIM == 2 ? fma(pc.c2, p, om) : fma(p, fma(pc.c2, om, pc.c3 * p), om * om);
+        const double v = (exp_node(fma(pc.e, log_node(om), ((r.B + Bc) + pc.lc) - Sx)) * poly) * W;
+        return isfinite(v) ? v : 0.0;
     } else if (COP == CVQ_PLACKETT) {
         const double u = r.z0, v = zc, th = S.theta;               // plackett.py:66-69 (Q11)
         const double num = th * (1.0 + (th - 1.0) * (u + v - 2.0 * u * v));
@@ -234,10 +345,10 @@ __device__ __forceinline__ double node_value(const StaticDev& S, const RowCtx& r
     return nan_to_num(c) * W;                                       // garch_integration_function.py:45-50
 }
 
-// The outer axes' B factors of a 3-D row combined (Gumbel's are logs, table_entry)
+// The outer axes' B factors of a 3-D row combined (the log-B kinds' are logs, table_entry)
 template <int COP>
 __device__ __forceinline__ double outer_B(double b0, double b1) {
-    if constexpr (COP == CVQ_GUMBEL) return b0 + b1;
+    if constexpr (kLogB<COP>) return b0 + b1;
     else return b0 * b1;
 }
 
@@ -247,7 +358,7 @@ __device__ __forceinline__ RowCtx make_row(const StaticDev& S, double z0, double
     r.z0 = z0;
     r.z1 = z1;
     r.B = B;
-    if (COP == CVQ_PLACKETT || COP == CVQ_GUMBEL) {
+    if (COP == CVQ_PLACKETT || kLogB<COP>) {
         r.p0 = r.p1 = r.p2 = 0.0;
         r.fin = true;
     } else if (DIM == 2) {

@@ -79,6 +79,7 @@ void quant_pass(const QuantLaunch& L) {
         case CVQ_STUDENT: quant_cop<CVQ_STUDENT, C>(L); break;
         case CVQ_PLACKETT: quant_cop<CVQ_PLACKETT, C>(L); break;
         case CVQ_GUMBEL: quant_cop<CVQ_GUMBEL, C>(L); break;
+        case CVQ_PRODFORM: quant_cop<CVQ_PRODFORM, C>(L); break;
         default: break;                                // launch_quantiles rejects unknown kinds
     }
 }
@@ -125,6 +126,7 @@ int launch_quantiles(const StaticDev& S, long long T, hipStream_t stream, const 
         case CVQ_STUDENT: if (msm) quant_tables<CVQ_STUDENT, true>(Q); else quant_tables<CVQ_STUDENT, false>(Q); break;
         case CVQ_PLACKETT: if (msm) quant_tables<CVQ_PLACKETT, true>(Q); else quant_tables<CVQ_PLACKETT, false>(Q); break;
         case CVQ_GUMBEL: if (msm) quant_tables<CVQ_GUMBEL, true>(Q); else quant_tables<CVQ_GUMBEL, false>(Q); break;
+        case CVQ_PRODFORM: if (msm) quant_tables<CVQ_PRODFORM, true>(Q); else quant_tables<CVQ_PRODFORM, false>(Q); break;
         default: CVQ_REQUIRE(false, CVQ_ERR_INVALID, "unknown copula kind");
     }
     CVQ_HIP_CHECK(hipGetLastError());

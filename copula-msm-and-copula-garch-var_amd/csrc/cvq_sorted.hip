@@ -35,13 +35,13 @@ int sorted_min_threads(int dim, int n) { return n > sorted_max_n_nt(dim, kSortNT
 // GPU runs 1024- or 512-thread dates, a full batch 256.  Counting whole workgroups per CU instead
 // (625 dates: 384 threads, every workgroup resident) measured slower than 512 threads with the
 // last ~100 dates starting late (cfg 3 133 vs 116 us, cfg 5 118 vs 103 us; profiles/r04o).
-// cop: the Gumbel kind's instances are compiled for fewer waves per SIMD (sorted_min_waves), so its
-// residency test counts those; the other kinds keep the width rule's generic value.
+// cop: the Gumbel and product-form kinds' instances are compiled for fewer waves per SIMD (sorted_min_waves), so
+// their residency test counts those; the other kinds keep the width rule's generic value.
 // forced: the plan's width (cvq_plan_set_sorted_threads, which admits none below
 // sorted_min_threads); 0: the rule.
 int sorted_threads(long long T, int dim, int n, int cop, int forced) {
     if (forced) return forced;
-    const int wcop = cop == CVQ_GUMBEL ? cop : -1;
+    const int wcop = (cop == CVQ_GUMBEL || cop == CVQ_PRODFORM) ? cop : -1;
     const int nt_min = sorted_min_threads(dim, n);
     for (int nt = 1024; nt > nt_min; nt >>= 1)
         if (T * (nt / 64) <= (long long)device_cus() * 4 * sorted_min_waves(dim, nt, wcop)) return nt;
@@ -54,12 +54,15 @@ int launch_sorted(const StaticDev& S, const SolveConst& P, const SortedGeom& G, 
                   int forced_nt, size_t abi) {
     CVQ_REQUIRE(abi == (kernel_abi_key() ^ (sizeof(SortedGeom) << 40)), CVQ_ERR_STATE,
                 "libcvq objects built from different headers (rebuild all)");
-    CVQ_REQUIRE(S.copula >= CVQ_GAUSSIAN && S.copula <= CVQ_GUMBEL, CVQ_ERR_INVALID, "unknown copula kind");
-    CVQ_REQUIRE(!(sweep && S.copula == CVQ_GUMBEL), CVQ_ERR_UNSUPPORTED, "the Gumbel copulas run on the SORTED strategy");
+    const bool logb = S.copula == CVQ_GUMBEL || S.copula == CVQ_PRODFORM;
+    CVQ_REQUIRE((S.copula >= CVQ_GAUSSIAN && S.copula <= CVQ_GUMBEL) || S.copula == CVQ_PRODFORM, CVQ_ERR_INVALID,
+                "unknown copula kind");
+    CVQ_REQUIRE(!(sweep && logb), CVQ_ERR_UNSUPPORTED,
+                "the Gumbel, Frank and Joe copulas run on the SORTED strategy");
     CVQ_REQUIRE(S.n <= sorted_max_n(S.dim), CVQ_ERR_UNSUPPORTED, "SORTED supports n <= 1024 (2-D) / 255 (3-D)");
     CVQ_REQUIRE(!(sweep && S.n > sorted_max_n_nt(S.dim, kSortNT)), CVQ_ERR_UNSUPPORTED, "SWEEP supports n <= 512");
     const SortedLaunch L{S, P, G, T, stream, a, tA, tB, pi, mode, bounds, out, snaps, hdr, fused, stamps, sweep};
-    CVQ_REQUIRE(!(S.copula == CVQ_GUMBEL && !fused), CVQ_ERR_STATE, "the Gumbel kind has fused-table instances only");
+    CVQ_REQUIRE(!(logb && !fused), CVQ_ERR_STATE, "the Gumbel and product-form kinds have fused-table instances only");
     const int nt = sorted_threads(T, S.dim, S.n, S.copula, forced_nt);
     CVQ_REQUIRE(nt >= sorted_min_threads(S.dim, S.n), CVQ_ERR_STATE, "SORTED width below what the grid needs");
     switch (nt) {

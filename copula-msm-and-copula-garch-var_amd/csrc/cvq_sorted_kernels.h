@@ -28,6 +28,8 @@
 //   Student   S0 B'1 B'2 (1 + z^T R^-1 z / nu)^-(nu+d)/2   (student.py:133-141)
 //   Gumbel    2^(sum L_i - A log2(e) + (1 - d theta) log2 A) poly_d(A), A = (sum x_i^theta)^(1/theta), from the
 //             per-axis records (x_i^theta, L_i = log2(pdf_i x_i^(theta-1) / u_i w_i)) (no reference)
+//   Frank/Joe 2^(sum L_i + log2(e) (lc - S + (kappa - d) log om)) poly_d(om, p), S = sum a_i, om = q0 - p0 expm1(-S),
+//             p = p0 e^-S, from Gumbel's record layout (a_i, L_i = log2(e) (B_i + log w_i)) (prod_const)
 // and otherwise the reference-semantics node (node_value, full W contraction,
 // garch_integration_function.py:45-50 nan_to_num).  3-D: the axis-0 weight
 // factor survives only on the plane i1 == 0 (create_grids.py:169-171, Q6) and
@@ -78,8 +80,9 @@ constexpr int kSortIlp = CVQ_SORT_ILP;                // nodes in flight per thr
 #endif
 __host__ __device__ constexpr int sorted_ilp(int cop, int pm, int dim, int nt = 256) {
     // (the Gumbel node -- log_node, exp_node, exp2_node7 -- carries the general-power Student
-    // node's temporaries and takes its setting)
-    return ((cop == CVQ_STUDENT && (pm == 0 || dim == 3)) || cop == CVQ_GUMBEL) ? CVQ_SORT_ILP_GEN
+    // node's temporaries and takes its setting; so does the product-form node -- exp_node with its
+    // series, log_node, exp2_node7)
+    return ((cop == CVQ_STUDENT && (pm == 0 || dim == 3)) || cop == CVQ_GUMBEL || cop == CVQ_PRODFORM) ? CVQ_SORT_ILP_GEN
          : (cop == CVQ_STUDENT && nt >= 512) ? CVQ_SORT_ILP_WIDE_ST : kSortIlp;
 }
 
@@ -270,7 +273,7 @@ inline size_t sorted_lds_bytes(int n, int nt, int dim, bool sweep = false, int l
 __host__ __device__ constexpr int sorted_min_waves(int dim, int nt = 256, int cop = -1, int pm = -1) {
     // (the Gumbel instances take 4 at every width: their table phase -- log, log1p, exp per entry --
     // and node spill 20-32 VGPRs at 5)
-    return cop == CVQ_GUMBEL ? CVQ_SORT_MIN_WAVES3
+    return (cop == CVQ_GUMBEL || cop == CVQ_PRODFORM) ? CVQ_SORT_MIN_WAVES3
          : dim == 2 ? ((nt >= 512 && !(cop == CVQ_STUDENT && pm == 0)) ? CVQ_SORT_MIN_WAVES2W : CVQ_SORT_MIN_WAVES2)
                     : CVQ_SORT_MIN_WAVES3;
 }
@@ -386,7 +389,7 @@ __global__ __launch_bounds__(NT, sorted_min_waves(DIM, NT, COP, PM)) void k_sort
             } else {
                 w = S.F[(size_t)ax * n + i];
             }
-            if constexpr (COP == CVQ_GUMBEL) {
+            if constexpr (kLogB<COP>) {
                 // a dead entry (A = NaN, both models) gets a +0 record below; a live one needs a
                 // finite log factor and a weight with a finite log
                 if (A == A && !(isfinite(B) && w > 0.0 && w < pos_inf())) bad |= 1;
@@ -470,7 +473,8 @@ __global__ __launch_bounds__(NT, sorted_min_waves(DIM, NT, COP, PM)) void k_sort
                 fr1[R1 * i + 1] = (L * k12) * z;
                 fg1[FG * i] = L * (lg(B * w) + kcc);
             }
-        } else if constexpr (COP == CVQ_GUMBEL) {
+        } else if constexpr (kLogB<COP>) {
+            // (product form: the generator value a and log2(e) (B + log w), the same layout)
             // (x^theta, log2(pdf x^(theta-1) / u  w)) per axis: the node adds the first parts into
             // S = A^theta and the second into its exponent.  A dead entry (table_entry: NaN, both
             // models) is (1, kGumbelDeadL): every node through it is 2^(-1e5 + ...) poly = +0 on the
@@ -551,6 +555,13 @@ __global__ __launch_bounds__(NT, sorted_min_waves(DIM, NT, COP, PM)) void k_sort
     // Gumbel node constants: 1 / theta, theta - 1, (1 - d theta) log2(e), poly_3's constant term
     const double gu_ith = 1.0 / S.theta, gu_t1 = S.theta - 1.0, gu_e = (1.0 - DIM * S.theta) * kLog2e,
                  gu_c3 = (S.theta - 1.0) * (2.0 * S.theta - 1.0);
+    // product-form node constants (prod_const), the exponent's scaled by log2(e)
+    ProdConst pr = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if constexpr (COP == CVQ_PRODFORM) {
+        pr = prod_const(S.survival, S.theta, DIM);
+        pr.e *= kLog2e;
+        pr.lc *= kLog2e;
+    }
     auto node_fast = [&](uint32_t c) -> double {
         const double2 A = rd2(rec0(c));
         const double2 C = rd2(rec2(c));
@@ -592,6 +603,24 @@ __global__ __launch_bounds__(NT, sorted_min_waves(DIM, NT, COP, PM)) void k_sort
             const double Av = exp_node(lA);
             const double poly = DIM == 2 ? Av + gu_t1 : fma(Av, Av + 3.0 * gu_t1, gu_c3);
             return exp2_node7(fma(gu_e, lA, fma(-kLog2e, Av, L))) * poly;
+        } else if constexpr (COP == CVQ_PRODFORM) {
+            // S sits in the exponent and in om: expm1 and log om from exp_node / its series and
+            // log_node (~1e-14), only the outer exponential from exp2_node7 (4e-11).  S >= kGumbelFloor,
+            // so om > 0 and every term is finite; poly_d has no division (node_value)
+            double Sx = A.x, L = A.y;
+            if constexpr (DIM == 3) {
+                const double2 Bv = rd2(rec1(c));
+                Sx += Bv.x;
+                L += Bv.y;
+            }
+            Sx += C.x;
+            L += C.y;
+            double ex;
+            const double E = expm1_neg_node(Sx, &ex);
+            const double om = fma(-pr.p0, E, pr.q0);
+            const double p = pr.p0 * ex;
+            const double poly = DIM == 2 ? fma(pr.c2, p, om) : fma(p, fma(pr.c2, om, pr.c3 * p), om * om);
+            return exp2_node7(fma(pr.e, log_node(om), fma(-kLog2e, Sx, L + pr.lc))) * poly;
         } else {                                           // Plackett, 2-D
             return plackett(A, C);
         }

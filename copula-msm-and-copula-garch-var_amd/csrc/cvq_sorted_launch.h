@@ -28,7 +28,7 @@ struct SortedLaunch {
 
 template <int NT, int COP, bool MSM, int DIM, int PM, bool FUSED, int LAY>
 void sorted_launch_l(const SortedLaunch& L) {
-    if constexpr (DIM == 2 && COP != CVQ_GUMBEL) {      // (no SWEEP instances of the Gumbel kinds: SORTED only)
+    if constexpr (DIM == 2 && !kLogB<COP>) {            // (no SWEEP instances of the log-B kinds: SORTED only)
         if (L.sweep && L.mode == 0) {                  // SWEEP: passes for the first levels (2-D solves)
             hipLaunchKernelGGL((k_sorted<COP, MSM, DIM, NT, PM, FUSED, LAY, true>), dim3((unsigned)L.T),
                                dim3(NT), sorted_lds_bytes(L.S.n, NT, DIM, true, LAY), L.stream, L.S, L.P,
@@ -53,10 +53,10 @@ void sorted_launch_f(const SortedLaunch& L) {
 
 template <int NT, int COP, bool MSM, int DIM, int PM>
 void sorted_launch_pm(const SortedLaunch& L) {
-    // the Gumbel kind builds its tables in the kernel only (no k_tables instance fills tA / tB:
-    // launch_sorted requires fused), so it has no FUSED = false instances
-    if (L.fused || COP == CVQ_GUMBEL) sorted_launch_f<NT, COP, MSM, DIM, PM, true>(L);
-    else if constexpr (COP != CVQ_GUMBEL) sorted_launch_f<NT, COP, MSM, DIM, PM, false>(L);
+    // the log-B kinds build their tables in the kernel only (no k_tables instance fills tA / tB:
+    // launch_sorted requires fused), so they have no FUSED = false instances
+    if (L.fused || kLogB<COP>) sorted_launch_f<NT, COP, MSM, DIM, PM, true>(L);
+    else if constexpr (!kLogB<COP>) sorted_launch_f<NT, COP, MSM, DIM, PM, false>(L);
 }
 
 template <int NT, int COP, bool MSM, int DIM>
@@ -92,6 +92,10 @@ void sorted_launch_nt(const SortedLaunch& L) {
         case CVQ_GUMBEL:                               // both Gumbel kinds (StaticDev::survival)
             if (L.S.model == CVQ_MSM) sorted_launch_m<NT, CVQ_GUMBEL, true>(L);
             else sorted_launch_m<NT, CVQ_GUMBEL, false>(L);
+            break;
+        case CVQ_PRODFORM:                             // Frank and both Joe kinds (StaticDev::survival)
+            if (L.S.model == CVQ_MSM) sorted_launch_m<NT, CVQ_PRODFORM, true>(L);
+            else sorted_launch_m<NT, CVQ_PRODFORM, false>(L);
             break;
         default: break;                                // launch_sorted rejects unknown kinds
     }

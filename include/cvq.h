@@ -46,6 +46,17 @@ extern "C" {
  * marginal CDF value is not strictly inside (0, 1) or the value is not finite (both models). */
 #define CVQ_GUMBEL          3
 #define CVQ_GUMBEL_SURVIVAL 4
+/* Product-form Archimedean kinds (no reference counterpart), copula_params = [theta],
+ * dim 2 or 3 (exchangeable), CVQ_STRATEGY_SORTED only, Gumbel's dead-node rule:
+ *   Frank  C(u) = -log(1 - prod_i (1 - e^(-theta u_i)) / (1 - e^(-theta))^(d-1)) / theta: no tail
+ *          dependence (radially symmetric for 2 assets).  0 < theta <= 32; theta = 0 or NaN is CVQ_ERR_INVALID,
+ *          theta < 0 (negative dependence) and theta > 32 are CVQ_ERR_UNSUPPORTED.
+ *   Joe    C(u) = 1 - (1 - prod_i (1 - (1 - u_i)^theta))^(1/theta): upper-tail dependent, and its
+ *          180-degree rotation c(1 - u) (survival Joe, lower-tail dependent).  1 <= theta <= 16,
+ *          with Gumbel's codes (theta < 1 or NaN: CVQ_ERR_INVALID; theta > 16: CVQ_ERR_UNSUPPORTED). */
+#define CVQ_FRANK        5
+#define CVQ_JOE          6
+#define CVQ_JOE_SURVIVAL 7
 /* model kinds: utils/model_estimation/model/{msm,garch,mean_reverting}_estimation.py */
 #define CVQ_MSM   0
 #define CVQ_GARCH 1
@@ -69,7 +80,7 @@ typedef struct cvq_plan cvq_plan;
  * consumed by calc_integral.py:8-119. */
 typedef struct cvq_static {
     int32_t model;              /* CVQ_MSM | CVQ_GARCH | CVQ_UKF                        */
-    int32_t copula;             /* CVQ_GAUSSIAN | CVQ_STUDENT | CVQ_PLACKETT | CVQ_GUMBEL[_SURVIVAL] */
+    int32_t copula;             /* CVQ_GAUSSIAN ... CVQ_JOE_SURVIVAL (the copula kinds above)        */
     int32_t dim;                /* assets: 2 or 3                                        */
     int32_t n;                  /* num_points                                            */
     int32_t q;                  /* unique vol states per asset (GARCH/UKF: 1)            */
@@ -81,7 +92,7 @@ typedef struct cvq_static {
     const double*  weights;     /* [dim]       host, weights[0] > 0                      */
     const double*  vol_states;  /* [dim][q]    host, MSM unique_vol_states; else NULL    */
     const double*  copula_params; /* packed as copula_integrations_params              */
-    int32_t n_copula_params;    /* Student 1+d(d-1)/2, Gaussian d(d-1)/2, Plackett 1, Gumbel 1 */
+    int32_t n_copula_params;    /* Student 1+d(d-1)/2, Gaussian d(d-1)/2, Plackett 1, Gumbel / Frank / Joe 1 */
     int32_t strategy;           /* CVQ_STRATEGY_*                                        */
     double  v_cap;              /* largest portfolio level any query may use (e.g. 0)    */
 } cvq_static;
@@ -325,7 +336,7 @@ int32_t cvq_portfolio_scratch(const cvq_plan* plan, int32_t n_portfolios, int32_
  * cvq_static.weights' convention (Q10); ptf_mean_t [T].  A NULL array means the plan's own value
  * (args->ptf_mean for the means) on every date; with all three NULL the call is cvq_quantiles, bit
  * for bit, and args->ptf_mean is read only when ptf_mean_t is NULL.  Fixed per plan: the copula
- * kind, the Gumbel survival flag and the Student nu (the t quantile tables and the integer-power
+ * kind (with the Gumbel / Joe survival flag) and the Student nu (the t quantile tables and the integer-power
  * paths hang on nu; copula_params_t[t][0] must repeat the plan's).
  * A date's result depends on its own record and inputs alone: not on the other dates, their
  * order or the number of levels, and it is bit-identical between runs (fixed-order sums; no
@@ -339,10 +350,10 @@ int32_t cvq_portfolio_scratch(const cvq_plan* plan, int32_t n_portfolios, int32_
  * offending date ("at date <t>") in cvq_last_error() and leaves the outputs unwritten:
  *   CVQ_ERR_INVALID: NULL plan, args, levels or var_out; n_levels outside 1..CVQ_MAX_LEVELS; a
  *     level <= 0 or NaN; max_var <= min_var; a non-finite parameter, weight or mean; Gumbel
- *     theta < 1; Student nu <= 0; Gaussian / Student: a correlation with |rho| >= 1, or a matrix
+ *     or Joe theta < 1; Frank theta = 0; Student nu <= 0; Gaussian / Student: a correlation with |rho| >= 1, or a matrix
  *     whose cofactor determinant is not > 0 -- stricter than cvq_plan_create, which takes any
  *     correlation values without this check;
- *   CVQ_ERR_UNSUPPORTED: Gumbel theta > 16; weights_t[t][0] <= 0; a Student
+ *   CVQ_ERR_UNSUPPORTED: Gumbel or Joe theta > 16; Frank theta < 0 or > 32; weights_t[t][0] <= 0; a Student
  *     copula_params_t[t][0] other than the plan's nu; K > 62;
  *   CVQ_ERR_STATE: called before cvq_set_dates. */
 int32_t cvq_dynamic_quantiles(cvq_plan* plan, const cvq_solve_args* args, const double* copula_params_t,
