@@ -31,6 +31,7 @@ FRANK, JOE, JOE_SURVIVAL = 5, 6, 7
 MSM, GARCH, UKF = 0, 1, 2
 STRATEGY_PREFIX, STRATEGY_DIRECT, STRATEGY_COMPACT, STRATEGY_SORTED, STRATEGY_SWEEP = 0, 1, 2, 3, 4
 MAX_PORTFOLIOS = 64                   # CVQ_MAX_PORTFOLIOS: weight vectors per cvq_portfolio_quantiles call
+MAX_BINS = 64                         # CVQ_MAX_BINS: level bins per cvq_distribution call
 
 COPULA_KIND = {"gaussian": GAUSSIAN, "student": STUDENT, "plackett": PLACKETT,
                "gumbel": GUMBEL, "gumbel_survival": GUMBEL_SURVIVAL,
@@ -93,6 +94,7 @@ def _declare(lib: C.CDLL) -> None:
         "cvq_slab_axis_moments": (i32, [v, v, v, v, i32]),
         "cvq_es_contributions": (i32, [v, C.POINTER(CvqSolveArgs), v, v, v, i32]),
         "cvq_quantiles": (i32, [v, C.POINTER(CvqSolveArgs), v, i32, v, v, v, i32]),
+        "cvq_distribution": (i32, [v, v, i32, i32, v, v, i32]),
         "cvq_conditional_quantiles": (i32, [v, C.POINTER(CvqSolveArgs), i32, v, v, i32, v, v, v, v, i32]),
         "cvq_portfolio_quantiles": (i32, [v, C.POINTER(CvqSolveArgs), v, v, i32, v, i32, v, v, v, i32]),
         "cvq_portfolio_scratch": (i32, [v, i32, i32, C.POINTER(i64)]),

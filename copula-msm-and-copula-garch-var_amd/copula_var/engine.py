@@ -475,6 +475,43 @@ class QuadraturePlan:
                                       C.c_void_p(es_ptr or 0), C.c_void_p(m0_ptr or 0), N.MEM_DEVICE),
                 "cvq_quantiles")
 
+    # ------------------------------------------------------------ predictive distribution (binned mass and moment)
+    # (no reference counterpart; like the moments it runs on this plan whatever its strategy)
+    def distribution(self, edges) -> Tuple[np.ndarray, np.ndarray]:
+        """(mass, m1), each (T, B): tail_moments of the B = len - 1 bins (e[b], e[b+1]] of a level
+        ladder, in one sweep per call.  A 1-D `edges` (B + 1,) serves every date, a 2-D one
+        (T, B + 1) is per date.  Each bin stands alone: edges need not ascend, a bin with a NaN
+        edge or with e[b+1] <= e[b] is exactly (0, 0), +-inf are valid edges; a bin's numbers do
+        not depend on the other bins or dates.  More than MAX_BINS bins are split into several
+        calls and concatenated (exact: bins are independent)."""
+        e = N.f64(edges)
+        if e.ndim not in (1, 2) or e.shape[-1] < 2 or (e.ndim == 2 and e.shape[0] != self.T):
+            raise ValueError(f"edges must have shape (B + 1,) or ({self.T}, B + 1) with B >= 1")
+        B = e.shape[-1] - 1
+        mass, m1 = np.empty((self.T, B)), np.empty((self.T, B))
+        for b0 in range(0, B, N.MAX_BINS):
+            nb = min(N.MAX_BINS, B - b0)
+            part = N.f64(e[..., b0:b0 + nb + 1])
+            o0, o1 = np.empty((self.T, nb)), np.empty((self.T, nb))
+            N.check(N.lib().cvq_distribution(self._h, N.ptr(part), nb, int(e.ndim == 2), N.ptr(o0), N.ptr(o1),
+                                             N.MEM_HOST), "cvq_distribution")
+            mass[:, b0:b0 + nb], m1[:, b0:b0 + nb] = o0, o1
+        return mass, m1
+
+    def distribution_device(self, edges, n_bins: int, mass_ptr: int, m1_ptr: Optional[int] = None) -> None:
+        """distribution into device buffers [T][n_bins] (at most MAX_BINS bins), in stream order:
+        no host synchronisation.  `edges`: a host sequence of n_bins + 1 numbers shared by every
+        date, or an int -- the device address of a per-date ladder [T][n_bins + 1]."""
+        if isinstance(edges, (int, np.integer)):
+            ep, per_date = C.c_void_p(int(edges)), 1
+        else:
+            e = N.f64(np.atleast_1d(np.asarray(edges, dtype=np.float64)))
+            if e.shape != (int(n_bins) + 1,):
+                raise ValueError("shared edges must have n_bins + 1 entries")
+            ep, per_date = N.ptr(e), 0
+        N.check(N.lib().cvq_distribution(self._h, ep, int(n_bins), per_date, C.c_void_p(mass_ptr),
+                                         C.c_void_p(m1_ptr or 0), N.MEM_DEVICE), "cvq_distribution")
+
     # ------------------------------------------------------------ conditional quantiles (CoVaR / CoES)
     def conditional_quantiles(self, axis: int, cond, levels, ptf_mean: float = 0.0, min_var=-7.5, max_var=0.0,
                               lower=-100.0, tolerance=1e-6

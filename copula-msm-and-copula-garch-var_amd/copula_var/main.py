@@ -11,6 +11,7 @@ Then, per estimation type, the pipeline main.py runs: factory -> ValueAtRiskCalc
 (in-sample fit, marginals, copula fit, forecasts) -> calc_var, all on the device.
 The VaR series (one column per estimation type) and the equal-weight portfolio
 returns go to --out; --plot saves main.py's plot_var_and_returns figure to a file.
+--backtest tests each VaR series against those portfolio returns (copula_var.backtest).
 """
 from __future__ import annotations
 
@@ -20,7 +21,7 @@ import sys
 import numpy as np
 import pandas as pd
 
-from . import dynamic, portfolios
+from . import backtest, dynamic, portfolios
 from .data_loader.load_data import SharedCacheIndexReturns, load_returns_csv
 from .utils.calc_var_class import ValueAtRiskCalcualtion
 from .utils.factory import ValueAtRiskCalculationFactory
@@ -97,6 +98,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--drift-weights", action="store_true",
                     help="the dvar / des columns follow a buy-and-hold portfolio: --weights on the first date, then "
                          "drifting with the realised returns (with or without --rolling-copula)")
+    ap.add_argument("--backtest", action="store_true",
+                    help="backtest each estimation's VaR against the realised portfolio returns (the plotted "
+                         "series): hit counts, Kupiec, Christoffersen, pinball score, Berkowitz on the PITs, "
+                         "Acerbi-Szekely's Z2 with --es, and one more table per level of --exact-levels; "
+                         "pit_<estimation> / hit_<estimation> columns in --out")
     return ap
 
 
@@ -122,6 +128,7 @@ def main(argv=None) -> int:
     if a.refit_every < 1:
         raise SystemExit("--refit-every: STEP must be >= 1")
     out, runs, es, esc, exact, covar, wbest, dyn = {}, {}, {}, {}, {}, {}, {}, {}
+    bt = {}
     for est in a.estimation:
         calc = ValueAtRiskCalculationFactory.create_var_calculator(copula_type=a.copula, estimation_type=est)
         kw = {"k": a.k} if est == "msm" else {}
@@ -178,6 +185,17 @@ def main(argv=None) -> int:
                       file=sys.stderr)
     first = runs[a.estimation[0]]
     portfolio = first.out_sample_data.mean(axis=1).to_numpy()                    # main.py:73
+    if a.backtest:
+        for est in a.estimation:
+            run = runs[est]
+            realised = portfolio[:run.plan.T]
+            table = run.backtest(realised, 0.05, var=out[est], es=es.get(est))
+            bt[est] = (run.last_pit, backtest.hits(realised, out[est]))
+            print(backtest.format_table(table, f"{est}/{a.copula} VaR"), file=sys.stderr)
+            for i, lv in enumerate(a.exact_levels or []):
+                table = backtest.backtest_table(realised, exact[est][0][:, i], es=exact[est][1][:, i],
+                                                pit=run.last_pit, alpha=lv)
+                print(backtest.format_table(table, f"{est}/{a.copula} exact VaR at {lv:g}"), file=sys.stderr)
     if a.out:
         idx = first.out_sample_data.index[:len(out[a.estimation[0]])]
         cols = {}
@@ -202,6 +220,9 @@ def main(argv=None) -> int:
                     cols[f"des_{k}_{lv:g}"] = dyn[k][1][:, i]
                 for j in range(dyn[k][2].shape[1]):
                     cols[f"dparam_{k}_{j}"] = dyn[k][2][:, j]
+            if k in bt:
+                cols[f"pit_{k}"] = bt[k][0]
+                cols[f"hit_{k}"] = np.where(bt[k][1]["keep"], (portfolio[:len(v)] < v).astype(np.float64), np.nan)
             if k in wbest:
                 for i, lv in enumerate(covar_levels):
                     for c, ticker in enumerate(a.tickers):

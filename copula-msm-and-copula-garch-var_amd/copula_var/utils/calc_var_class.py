@@ -165,6 +165,32 @@ class ValueAtRiskCalcualtion:
         var, es, self.last_tail_mass = self.plan.quantiles(levels, self.ptf_mean)
         return var, es
 
+    def calc_distribution(self, edges):
+        """(mass, m1), each (T, B): the mass and first moment of the nested-grid measure in the bins
+        (edges[b], edges[b+1]] of a ladder of portfolio returns (ptf_mean included, as calc_var's
+        values are) -- (B + 1,) for every date or (T, B + 1) per date -- all bins in one device
+        sweep (no reference counterpart).  m1 is in centred levels, as expected_shortfall's m1.
+        The measure is not normalised: divide by the bin sum up to +inf for probabilities."""
+        return self.plan.distribution(np.asarray(edges, dtype=np.float64) - self.ptf_mean)
+
+    def calc_pit(self, realised):
+        """u (T,): the probability integral transform F_t(r_t) / F_t(+inf) of each date's realised
+        portfolio return under that date's forecast (no reference counterpart); NaN where the
+        return is NaN."""
+        from ..backtest import pit
+        return pit(self.plan, realised, self.ptf_mean)
+
+    def backtest(self, realised, alpha=0.05, var=None, es=None):
+        """The backtest table (copula_var.backtest.backtest_table) of a VaR series against the
+        realised portfolio returns (T,): hit counts, Kupiec, Christoffersen, the pinball score,
+        Berkowitz on this run's PITs and, when `es` is given, Acerbi-Szekely's Z2.  var=None solves
+        calc_var at obj_var = alpha first.  The PITs are kept in last_pit."""
+        from ..backtest import backtest_table
+        if var is None:
+            var = self.calc_var(alpha)
+        self.last_pit = self.calc_pit(realised)
+        return backtest_table(realised, var, es=es, pit=self.last_pit, alpha=alpha)
+
     def calc_portfolio_quantiles(self, weights, levels=(0.05,)):
         """(var, es), each (T, P, L): calc_quantiles for P candidate weight vectors (P, dim) on this
         run's fitted measure, all candidates in one device call per 64 (no reference

@@ -160,6 +160,11 @@ struct cvq_plan {
     // marginal tables are the moments' d_mA / d_mB
     size_t capQuant = 0;
     double* d_qwork = nullptr;
+    // predictive distribution (cvq_distribution): per-(date, chunk, bin) partial pairs, then the
+    // host-mode staging of the per-date edges and the two outputs; the marginal tables are the
+    // moments' d_mA / d_mB
+    size_t capDist = 0;
+    double* d_dist = nullptr;
     // risk contributions (cvq_slab_axis_moments / cvq_es_contributions): per-chunk partial sums
     // [T][chunks][1 + dim]; the marginal tables are the moments' d_mA / d_mB
     size_t capAttr = 0;
@@ -894,6 +899,11 @@ int launch_quantiles(const StaticDev& S, long long T, hipStream_t stream, const 
                      double* tA, double* tB, double* work, const double* alpha, int L, int K, double min_var,
                      double max_var, double lower, double ptf_mean, double* var_out, double* es_out, double* m0_out,
                      size_t abi);
+int distribution_check(const StaticDev& S);                                           // cvq_distribution.hip
+size_t distribution_scratch(int dim, int nrows, int nb);
+int launch_distribution(const StaticDev& S, long long T, hipStream_t stream, const double* a, const double* pi,
+                        double* tA, double* tB, double* part, const double* edges, const double* shared, int nb,
+                        double* mass_out, double* m1_out, size_t abi);
 size_t conditional_scratch(int dim, int nrows);                                       // cvq_conditional.hip
 int launch_conditional(const StaticDev& S, long long T, hipStream_t stream, const double* a, const double* pi,
                        double* tA, double* tB, double* work, int axis, const double* cond, const double* alpha, int L,
@@ -1235,6 +1245,26 @@ int run_quantiles(cvq_plan* p, const cvq_solve_args& a, int K, const double* lev
     TimedScope ts(p, TK_QUANTILES);
     return launch_quantiles(p->S, p->T, p->stream, p->in_a, p->in_pi, p->d_mA, p->d_mB, p->d_qwork, levels, L, K,
                             a.min_var, a.max_var, a.lower, a.ptf_mean, var, es, m0, kernel_abi_key());
+}
+
+// Predictive distribution: the moments' table scratch + a work buffer of their own (`extra`
+// doubles behind the partial sums: the host mode's staging), timed with the tail moments (kind 5).
+int ensure_distribution(cvq_plan* p, int nb, size_t extra) {
+    int rc = ensure_moments(p);
+    if (rc) return rc;
+    const size_t need = (size_t)p->T * distribution_scratch(p->S.dim, p->S.nrows, nb) + extra;
+    if (need > p->capDist) {
+        p->capDist = 0;
+        if ((rc = dev_alloc(&p->d_dist, need))) return rc;
+        p->capDist = need;
+    }
+    return CVQ_OK;
+}
+
+int run_distribution(cvq_plan* p, const double* edges, const double* shared, int nb, double* mass, double* m1) {
+    TimedScope ts(p, TK_MOMENTS);
+    return launch_distribution(p->S, p->T, p->stream, p->in_a, p->in_pi, p->d_mA, p->d_mB, p->d_dist, edges, shared,
+                               nb, mass, m1, kernel_abi_key());
 }
 
 // Conditional quantiles: the moments' table scratch + a work buffer of their own, then the
@@ -1674,7 +1704,8 @@ int32_t cvq_plan_destroy(cvq_plan* p) {
                     (void*)p->d_mA, (void*)p->d_mB, (void*)p->d_mpart, (void*)p->d_qwork, (void*)p->d_apart,
                     (void*)p->d_cutfix, (void*)p->d_kcut, (void*)p->d_fpair, (void*)p->d_ccount, (void*)p->d_tlist, (void*)p->d_tvs, (void*)p->d_defer, (void*)p->d_vstar, (void*)p->d_bucket, (void*)p->d_sidx, (void*)p->d_svs,
                     (void*)p->d_tree, (void*)p->d_pass,
-                    (void*)p->d_pidx, (void*)p->d_pvs, (void*)p->d_cwork, (void*)p->d_pwork, (void*)p->d_dwork})
+                    (void*)p->d_pidx, (void*)p->d_pvs, (void*)p->d_cwork, (void*)p->d_pwork, (void*)p->d_dwork,
+                    (void*)p->d_dist})
         if (b) (void)hipFree(b);
     for (auto& st : p->dyn_stage) { (void)hipEventDestroy(st.done); (void)hipHostFree(st.h); }
     if (p->own_stream) (void)hipStreamDestroy(p->own_stream);
@@ -1978,6 +2009,37 @@ int32_t cvq_quantiles(cvq_plan* p, const cvq_solve_args* a, const double* levels
         CVQ_HIP_CHECK(hipMemcpyAsync(es_out, p->d_io + TL, TL * sizeof(double), hipMemcpyDeviceToHost, p->stream));
     if (m0_out)
         CVQ_HIP_CHECK(hipMemcpyAsync(m0_out, p->d_io + 2 * TL, TL * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    CVQ_HIP_CHECK(hipStreamSynchronize(p->stream));
+    return CVQ_OK;
+}
+
+int32_t cvq_distribution(cvq_plan* p, const double* edges, int32_t n_bins, int32_t per_date, double* mass_out,
+                         double* m1_out, int32_t mem) {
+    cvq::DeviceScope device_scope;                 // the caller's current device, restored on return
+    // arguments first, the plan last: all of it is checked on the host before any device work
+    CVQ_REQUIRE(edges != nullptr && mass_out != nullptr, CVQ_ERR_INVALID, "NULL argument");
+    CVQ_REQUIRE(n_bins >= 1 && n_bins <= CVQ_MAX_BINS, CVQ_ERR_INVALID, "n_bins must be in [1, CVQ_MAX_BINS]");
+    CVQ_REQUIRE(per_date == 0 || per_date == 1, CVQ_ERR_INVALID, "per_date must be 0 or 1");
+    CVQ_REQUIRE(p != nullptr, CVQ_ERR_INVALID, "plan is NULL");
+    CVQ_REQUIRE(p->T > 0, CVQ_ERR_STATE, "cvq_set_dates must be called first");
+    int rc = distribution_check(p->S);
+    if (rc) return rc;
+    CVQ_HIP_CHECK(hipSetDevice(p->device));
+    const long long T = p->T;
+    const size_t TB = (size_t)T * n_bins, TE = (size_t)T * (n_bins + 1);
+    if (mem == CVQ_MEM_DEVICE) {
+        if ((rc = ensure_distribution(p, n_bins, 0))) return rc;
+        return run_distribution(p, per_date ? edges : nullptr, edges, n_bins, mass_out, m1_out);
+    }
+    if ((rc = ensure_distribution(p, n_bins, TE + 2 * TB))) return rc;
+    double* d_edges = p->d_dist + (size_t)T * distribution_scratch(p->S.dim, p->S.nrows, n_bins);
+    double* d_mass = d_edges + TE;
+    double* d_m1 = m1_out ? d_mass + TB : nullptr;
+    if (per_date)
+        CVQ_HIP_CHECK(hipMemcpyAsync(d_edges, edges, TE * sizeof(double), hipMemcpyHostToDevice, p->stream));
+    if ((rc = run_distribution(p, per_date ? d_edges : nullptr, edges, n_bins, d_mass, d_m1))) return rc;
+    CVQ_HIP_CHECK(hipMemcpyAsync(mass_out, d_mass, TB * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    if (m1_out) CVQ_HIP_CHECK(hipMemcpyAsync(m1_out, d_m1, TB * sizeof(double), hipMemcpyDeviceToHost, p->stream));
     CVQ_HIP_CHECK(hipStreamSynchronize(p->stream));
     return CVQ_OK;
 }

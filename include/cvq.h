@@ -130,7 +130,7 @@ int32_t cvq_plan_info(const cvq_plan* plan, int64_t* reach_nodes, int32_t* rows)
  * live roofline).  kind: 0 tables, 1 joint-mass/prefix, 2 solve, 3 finalize,
  * 4 slab, 5 tail moments (cvq_slab_moments / cvq_expected_shortfall and the axis moments
  * cvq_slab_axis_moments / cvq_es_contributions: their tables,
- * partial sums and finish together), 6 exact quantiles (cvq_quantiles and its conditional,
+ * partial sums and finish together; cvq_distribution likewise), 6 exact quantiles (cvq_quantiles and its conditional,
  * batched-weights and per-date-record forms: their tables, passes and updates together).
  * cvq_plan_timing(mask) times the kinds whose bit (1 << kind) is
  * set (0 = off, 0x7F = all) and clears previous records. */
@@ -260,6 +260,36 @@ int32_t cvq_es_contributions(cvq_plan* plan, const cvq_solve_args* args, const d
 #define CVQ_MAX_LEVELS 8
 int32_t cvq_quantiles(cvq_plan* plan, const cvq_solve_args* args, const double* levels, int32_t n_levels,
                       double* var_out, double* es_out, double* m0_out, int32_t mem);
+
+/* No reference counterpart.  The predictive distribution of the portfolio return: per date, the
+ * mass and first moment of the nested-grid measure in up to CVQ_MAX_BINS level bins in one
+ * sweep -- the value-to-level direction that cvq_quantiles lacks (a PIT is two bins, a CDF at K
+ * thresholds K + 1).  Bin b of date t is the slab (e[b], e[b+1]] under cvq_slab_moments'
+ * membership rule and node masses:
+ *   mass_out[t][b] = that slab's m0,  m1_out[t][b] = its m1  (cvq_slab_moments' values to
+ *   rounding: the summation order differs).
+ * per_date == 0: edges is host [n_bins + 1] whatever `mem` says and serves every date;
+ * per_date == 1: edges is [T][n_bins + 1], host|device.  mass_out / m1_out [T][n_bins]
+ * host|device; m1_out may be NULL.
+ * Each bin stands alone: edges need not ascend; a bin with a NaN edge or with e[b+1] <= e[b] is
+ * exactly (0, 0); +-inf edges are valid (every node, or none, lies at or below them).  The measure
+ * is not normalised (quirks Q5/Q6): the total mass is the bin (lower, +inf].
+ * A bin's two numbers depend on its own two edges and its date's inputs alone -- not on the other
+ * bins of the call, their number or order, nor on the other dates -- and are bit-identical between
+ * runs (fixed-order sums, no atomics).  The marginal tables are built once per call and the row
+ * setup once per row; with an ascending ladder every quadrature node is evaluated once.
+ * Runs on every strategy with no v_cap limit, on lazily sized scratch of its own: the plan's
+ * solve state is untouched.  CVQ_MEM_DEVICE is stream-ordered without a host synchronisation.
+ * Timed under kind 5 (tail moments).
+ *   CVQ_ERR_INVALID: NULL plan, edges or mass_out; n_bins outside 1..CVQ_MAX_BINS; per_date not
+ *     0 or 1.
+ *   CVQ_ERR_STATE: called before cvq_set_dates.
+ *   CVQ_ERR_UNSUPPORTED: a grid outside cvq_quantiles' limits (n <= 1024, q <= 8, dim 2 or 3,
+ *     Plackett 2-D only).
+ * All of them are found on the host before any device work. */
+#define CVQ_MAX_BINS 64
+int32_t cvq_distribution(cvq_plan* plan, const double* edges, int32_t n_bins, int32_t per_date,
+                         double* mass_out, double* m1_out, int32_t mem);
 
 /* No reference counterpart.  Conditional quantiles of the nested-grid measure: CoVaR / CoES of
  * the portfolio given an event on one grid axis (Adrian-Brunnermeier; the "<=" form of
