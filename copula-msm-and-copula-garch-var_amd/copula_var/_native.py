@@ -100,6 +100,7 @@ def _declare(lib: C.CDLL) -> None:
         "cvq_portfolio_scratch": (i32, [v, i32, i32, C.POINTER(i64)]),
         "cvq_dynamic_quantiles": (i32, [v, C.POINTER(CvqSolveArgs), v, v, v, v, i32, v, v, v, i32]),
         "cvq_dynamic_scratch": (i32, [v, i32, C.POINTER(i64)]),
+        "cvq_dynamic_distribution": (i32, [v, v, v, v, i32, i32, v, v, i32]),
         "cvq_solve": (i32, [v, C.POINTER(CvqSolveArgs), v, _ip, i32]),
         "cvq_snap_stride": (i32, [C.POINTER(CvqSolveArgs), _ip]),
         "cvq_solve_status": (i32, [v, _ip]),

@@ -2,7 +2,9 @@
 reference plots its VaR series next to the returns and stops there).
 
 Two device-backed pieces, both on QuadraturePlan.distribution (cvq_distribution: the mass of the
-nested-grid measure in many level bins per date in one sweep):
+nested-grid measure in many level bins per date in one sweep), or on
+QuadraturePlan.dynamic_distribution where the forecast has per-date copula parameters, weights or
+means (the model behind dynamic_quantiles):
 
   predictive_cdf  -- F_t at K thresholds per date;
   pit             -- u_t = F_t(r_t) / F_t(+inf), the probability integral transform of a
@@ -29,33 +31,61 @@ PIT_CLIP = 1e-12          # berkowitz: u is clipped to [PIT_CLIP, 1 - PIT_CLIP] 
 
 
 # ------------------------------------------------------------------ device-backed pieces
-def predictive_cdf(plan, thresholds, ptf_mean: float = 0.0, lower: float = -100.0):
+def _per_date(plan, ptf_mean, copula_params, weights):
+    """(dynamic, mean): whether the call goes to plan.dynamic_distribution (per-date parameters,
+    weights or means), and the mean as given (scalar) or as a checked (T,) vector."""
+    m = np.asarray(ptf_mean, dtype=np.float64)
+    if m.ndim == 0:
+        return copula_params is not None or weights is not None, ptf_mean
+    if m.shape != (plan.T,):
+        raise ValueError(f"ptf_mean must be a scalar or have shape ({plan.T},)")
+    return True, m
+
+
+def predictive_cdf(plan, thresholds, ptf_mean=0.0, lower: float = -100.0, copula_params=None, weights=None):
     """(F (T, K), total (T,)): the normalised predictive CDF of the portfolio return at K
     ascending thresholds (returns, ptf_mean included) -- shared by every date (K,) or per date
     (T, K).  The ladder is [lower, thresholds - ptf_mean ..., +inf]; F is the running sum of the
-    bin masses divided by `total`, the sum of all K + 1 bins.  F is NaN where total == 0."""
+    bin masses divided by `total`, the sum of all K + 1 bins.  F is NaN where total == 0.
+    copula_params (T, n_copula_params) / weights (T, dim) / a (T,) ptf_mean: the forecast of
+    plan.dynamic_quantiles, every date under its own parameters, weights and mean
+    (plan.dynamic_distribution); with both None and a scalar mean the plan's static model
+    (plan.distribution)."""
     th = np.asarray(thresholds, dtype=np.float64)
     if th.ndim not in (1, 2) or th.shape[-1] < 1:
         raise ValueError("thresholds must have shape (K,) or (T, K) with K >= 1")
+    dynamic, mean = _per_date(plan, ptf_mean, copula_params, weights)
+    if np.ndim(mean) == 1:                            # a ladder per date, each centred on its own mean
+        th = np.broadcast_to(th, (plan.T, th.shape[-1])) - mean[:, None]
+    else:
+        th = th - mean
     lead = th.shape[:-1]
-    edges = np.concatenate((np.full(lead + (1,), float(lower)), th - ptf_mean, np.full(lead + (1,), np.inf)), axis=-1)
-    mass, _ = plan.distribution(edges)
+    edges = np.concatenate((np.full(lead + (1,), float(lower)), th, np.full(lead + (1,), np.inf)), axis=-1)
+    if dynamic:
+        mass, _ = plan.dynamic_distribution(edges, copula_params=copula_params, weights=weights)
+    else:
+        mass, _ = plan.distribution(edges)
     total = mass.sum(axis=1)
     with np.errstate(invalid="ignore", divide="ignore"):
         F = np.where(total[:, None] != 0.0, np.cumsum(mass[:, :-1], axis=1) / total[:, None], np.nan)
     return F, total
 
 
-def pit(plan, realised, ptf_mean: float = 0.0, lower: float = -100.0) -> np.ndarray:
+def pit(plan, realised, ptf_mean=0.0, lower: float = -100.0, copula_params=None, weights=None) -> np.ndarray:
     """u (T,): the probability integral transform of each date's realised portfolio return
     (ptf_mean included) under that date's forecast, u = bin0 / (bin0 + bin1) over the per-date
     ladder [lower, realised[t] - ptf_mean, +inf].  NaN where the return is NaN or the total
-    mass is 0."""
+    mass is 0.  copula_params / weights / a (T,) ptf_mean as in predictive_cdf: the PIT under the
+    per-date model that plan.dynamic_quantiles forecasts with."""
     r = np.asarray(realised, dtype=np.float64)
     if r.shape != (plan.T,):
         raise ValueError(f"realised must have shape ({plan.T},)")
-    edges = np.column_stack((np.full(r.size, float(lower)), r - ptf_mean, np.full(r.size, np.inf)))
-    mass, _ = plan.distribution(edges)
+    dynamic, mean = _per_date(plan, ptf_mean, copula_params, weights)
+    edges = np.column_stack((np.full(r.size, float(lower)), r - mean, np.full(r.size, np.inf)))
+    if dynamic:
+        mass, _ = plan.dynamic_distribution(edges, copula_params=copula_params, weights=weights)
+    else:
+        mass, _ = plan.distribution(edges)
     total = mass[:, 0] + mass[:, 1]
     with np.errstate(invalid="ignore", divide="ignore"):
         return np.where(np.isnan(r) | (total == 0.0), np.nan, mass[:, 0] / total)

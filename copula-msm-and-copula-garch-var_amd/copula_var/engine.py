@@ -667,6 +667,51 @@ class QuadraturePlan:
                                               C.c_void_p(var_ptr), C.c_void_p(es_ptr or 0), C.c_void_p(m0_ptr or 0),
                                               N.MEM_DEVICE), "cvq_dynamic_quantiles")
 
+    # ------------------------------------------------------------ distribution under per-date records
+    def dynamic_distribution(self, edges, copula_params=None, weights=None) -> Tuple[np.ndarray, np.ndarray]:
+        """(mass, m1), each (T, B): `distribution` where every date has copula parameters and
+        weights of its own (dynamic_quantiles' arrays and shape rules; None keeps the plan's own on
+        every date).  [t] is bit for bit what `distribution` returns on a plan built with date t's
+        parameters and weights; with both None it is `distribution`.  Edges are centred levels, (B + 1,)
+        for every date or (T, B + 1) per date: a caller with per-date means subtracts them from a
+        per-date ladder.  More than MAX_BINS bins are split into several calls and concatenated
+        (exact: bins are independent).  ValueError names the first bad date."""
+        e = N.f64(edges)
+        if e.ndim not in (1, 2) or e.shape[-1] < 2 or (e.ndim == 2 and e.shape[0] != self.T):
+            raise ValueError(f"edges must have shape (B + 1,) or ({self.T}, B + 1) with B >= 1")
+        _, cp, w, _ = self._dynamic_inputs(0.5, copula_params, weights, 0.0)
+        B = e.shape[-1] - 1
+        mass, m1 = np.empty((self.T, B)), np.empty((self.T, B))
+        for b0 in range(0, B, N.MAX_BINS):
+            nb = min(N.MAX_BINS, B - b0)
+            part = N.f64(e[..., b0:b0 + nb + 1])
+            o0, o1 = np.empty((self.T, nb)), np.empty((self.T, nb))
+            N.check(N.lib().cvq_dynamic_distribution(self._h, N.ptr(cp) if cp is not None else None,
+                                                     N.ptr(w) if w is not None else None, N.ptr(part), nb,
+                                                     int(e.ndim == 2), N.ptr(o0), N.ptr(o1), N.MEM_HOST),
+                    "cvq_dynamic_distribution")
+            mass[:, b0:b0 + nb], m1[:, b0:b0 + nb] = o0, o1
+        return mass, m1
+
+    def dynamic_distribution_device(self, edges, n_bins: int, mass_ptr: int, m1_ptr: Optional[int] = None,
+                                    copula_params=None, weights=None) -> None:
+        """dynamic_distribution into device buffers [T][n_bins] (at most MAX_BINS bins), in stream
+        order: no host synchronisation.  `edges` as in distribution_device: a host sequence of
+        n_bins + 1 numbers shared by every date, or an int -- the device address of a per-date
+        ladder [T][n_bins + 1].  The per-date arrays stay on the host and may be dropped on return."""
+        _, cp, w, _ = self._dynamic_inputs(0.5, copula_params, weights, 0.0)
+        if isinstance(edges, (int, np.integer)):
+            ep, per_date = C.c_void_p(int(edges)), 1
+        else:
+            e = N.f64(np.atleast_1d(np.asarray(edges, dtype=np.float64)))
+            if e.shape != (int(n_bins) + 1,):
+                raise ValueError("shared edges must have n_bins + 1 entries")
+            ep, per_date = N.ptr(e), 0
+        N.check(N.lib().cvq_dynamic_distribution(self._h, N.ptr(cp) if cp is not None else None,
+                                                 N.ptr(w) if w is not None else None, ep, int(n_bins), per_date,
+                                                 C.c_void_p(mass_ptr), C.c_void_p(m1_ptr or 0), N.MEM_DEVICE),
+                "cvq_dynamic_distribution")
+
     # ------------------------------------------------------------ device-resident solve
     def solve_device(self, args: N.CvqSolveArgs, var_ptr: int, check: bool = False) -> Optional[int]:
         """calc_var into a device buffer.  check=False: in stream order, no host

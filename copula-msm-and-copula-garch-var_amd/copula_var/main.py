@@ -11,7 +11,8 @@ Then, per estimation type, the pipeline main.py runs: factory -> ValueAtRiskCalc
 (in-sample fit, marginals, copula fit, forecasts) -> calc_var, all on the device.
 The VaR series (one column per estimation type) and the equal-weight portfolio
 returns go to --out; --plot saves main.py's plot_var_and_returns figure to a file.
---backtest tests each VaR series against those portfolio returns (copula_var.backtest).
+--backtest tests each VaR series against those portfolio returns (copula_var.backtest), the
+dynamic ones (--rolling-copula, --drift-weights) under their own per-date predictive distribution.
 """
 from __future__ import annotations
 
@@ -102,7 +103,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="backtest each estimation's VaR against the realised portfolio returns (the plotted "
                          "series): hit counts, Kupiec, Christoffersen, pinball score, Berkowitz on the PITs, "
                          "Acerbi-Szekely's Z2 with --es, and one more table per level of --exact-levels; "
-                         "pit_<estimation> / hit_<estimation> columns in --out")
+                         "pit_<estimation> / hit_<estimation> columns in --out.  With --rolling-copula or "
+                         "--drift-weights: one more table per level for the dvar / des columns, with Berkowitz on "
+                         "the PITs of the per-date model that produced them (not the static one); "
+                         "dpit_<estimation> / dhit_<estimation>_<level> columns in --out")
     return ap
 
 
@@ -128,7 +132,7 @@ def main(argv=None) -> int:
     if a.refit_every < 1:
         raise SystemExit("--refit-every: STEP must be >= 1")
     out, runs, es, esc, exact, covar, wbest, dyn = {}, {}, {}, {}, {}, {}, {}, {}
-    bt = {}
+    bt, dbt, dyn_w = {}, {}, {}
     for est in a.estimation:
         calc = ValueAtRiskCalculationFactory.create_var_calculator(copula_type=a.copula, estimation_type=est)
         kw = {"k": a.k} if est == "msm" else {}
@@ -180,6 +184,7 @@ def main(argv=None) -> int:
             if a.drift_weights:
                 wt = dynamic.drift_weights(run.out_sample_data.to_numpy(dtype=np.float64)[:T], weights)
             dyn[est] = run.calc_dynamic_quantiles(a.exact_levels, copula_params=path, weights=wt) + (path,)
+            dyn_w[est] = wt
             for i, lv in enumerate(a.exact_levels):
                 print(f"{est}/{a.copula}: mean dynamic VaR at {lv:g}: {np.nanmean(dyn[est][0][:, i]):.4f}",
                       file=sys.stderr)
@@ -196,6 +201,19 @@ def main(argv=None) -> int:
                 table = backtest.backtest_table(realised, exact[est][0][:, i], es=exact[est][1][:, i],
                                                 pit=run.last_pit, alpha=lv)
                 print(backtest.format_table(table, f"{est}/{a.copula} exact VaR at {lv:g}"), file=sys.stderr)
+            if est in dyn:                          # the per-date model's own PITs, one sweep for every level
+                dvar, des, path = dyn[est]
+                dhits = []
+                for i, lv in enumerate(a.exact_levels):
+                    if i == 0:
+                        table = run.dynamic_backtest(realised, lv, dvar[:, 0], es=des[:, 0], copula_params=path,
+                                                     weights=dyn_w[est])
+                    else:
+                        table = backtest.backtest_table(realised, dvar[:, i], es=des[:, i],
+                                                        pit=run.last_dynamic_pit, alpha=lv)
+                    dhits.append(backtest.hits(realised, dvar[:, i]))
+                    print(backtest.format_table(table, f"{est}/{a.copula} dynamic VaR at {lv:g}"), file=sys.stderr)
+                dbt[est] = (run.last_dynamic_pit, dhits)
     if a.out:
         idx = first.out_sample_data.index[:len(out[a.estimation[0]])]
         cols = {}
@@ -223,6 +241,12 @@ def main(argv=None) -> int:
             if k in bt:
                 cols[f"pit_{k}"] = bt[k][0]
                 cols[f"hit_{k}"] = np.where(bt[k][1]["keep"], (portfolio[:len(v)] < v).astype(np.float64), np.nan)
+            if k in dbt:
+                cols[f"dpit_{k}"] = dbt[k][0]
+                for i, lv in enumerate(a.exact_levels):
+                    dv = dyn[k][0][:, i]
+                    cols[f"dhit_{k}_{lv:g}"] = np.where(dbt[k][1][i]["keep"],
+                                                        (portfolio[:len(dv)] < dv).astype(np.float64), np.nan)
             if k in wbest:
                 for i, lv in enumerate(covar_levels):
                     for c, ticker in enumerate(a.tickers):

@@ -234,6 +234,47 @@ class ValueAtRiskCalcualtion:
                                                                    self.dynamic_ptf_mean(weights))
         return var, es
 
+    def _dynamic_weights(self, weights):
+        if weights is None:
+            return None
+        weights = np.asarray(weights, dtype=np.float64)
+        if weights.shape != (self.plan.T, self.dim):
+            raise ValueError(f"weights must have shape ({self.plan.T}, {self.dim})")
+        return weights
+
+    def calc_dynamic_distribution(self, edges, copula_params=None, weights=None):
+        """(mass, m1), each (T, B): calc_distribution under calc_dynamic_quantiles' per-date copula
+        parameters and weights (no reference counterpart).  edges are portfolio returns, the
+        date's own mean included (dynamic_ptf_mean of that date's weights), (B + 1,) for every date
+        or (T, B + 1) per date.  Row t is what calc_distribution returns for date t from a run
+        constructed with those parameters and weights.  All dates in one device sweep."""
+        weights = self._dynamic_weights(weights)
+        e = np.asarray(edges, dtype=np.float64)
+        mean = self.dynamic_ptf_mean(weights)
+        if np.ndim(mean) == 1:
+            e = np.broadcast_to(e, (self.plan.T, e.shape[-1])) - mean[:, None]
+        else:
+            e = e - mean
+        return self.plan.dynamic_distribution(e, copula_params, weights)
+
+    def calc_dynamic_pit(self, realised, copula_params=None, weights=None):
+        """u (T,): calc_pit under calc_dynamic_quantiles' per-date model -- the PIT of each date's
+        realised portfolio return under the forecast that produced that date's dynamic VaR (no
+        reference counterpart); NaN where the return is NaN."""
+        from ..backtest import pit
+        weights = self._dynamic_weights(weights)
+        return pit(self.plan, realised, self.dynamic_ptf_mean(weights), copula_params=copula_params,
+                   weights=weights)
+
+    def dynamic_backtest(self, realised, alpha, var, es=None, copula_params=None, weights=None):
+        """The backtest table of a calc_dynamic_quantiles VaR series (T,) at level alpha against
+        the realised portfolio returns: `backtest` with Berkowitz on the PITs of the per-date
+        model (calc_dynamic_pit with the same copula_params and weights), kept in
+        last_dynamic_pit."""
+        from ..backtest import backtest_table
+        self.last_dynamic_pit = self.calc_dynamic_pit(realised, copula_params, weights)
+        return backtest_table(realised, var, es=es, pit=self.last_dynamic_pit, alpha=alpha)
+
     def oos_pits(self):
         """(u, pdf), each (T, dim): the forecast marginals' CDF and density at the realised centred
         return of every out-of-sample date (copula_var.dynamic.oos_pits on this run's forecasts)."""

@@ -186,6 +186,11 @@ struct cvq_plan {
     double* d_dwork = nullptr;
     struct DynStage { double* h; size_t cap; hipEvent_t done; };
     std::vector<DynStage> dyn_stage;
+    // per-date-record distribution (cvq_dynamic_distribution): the call's date records, the
+    // per-(date, chunk, bin) partial pairs, then the host mode's staging (edges, two outputs); the
+    // marginal tables are the moments', the records travel through dyn_stage
+    size_t capDynDist = 0;
+    double* d_ddist = nullptr;
     unsigned long long* d_stamps = nullptr;   // diagnostic phase stamps (CVQ_STAMPS=1)
     bool count_nodes = false;    // cvq_plan_count_nodes: solves record their node counts (stamps)
     bool nodes_valid = false;    // the last solve recorded them
@@ -921,6 +926,11 @@ void dynamic_pack(double* recs, long long t, double theta, double term1, const d
 int launch_dynamic(const StaticDev& S, long long T, hipStream_t stream, const double* a, const double* pi,
                    double* tA, double* tB, double* work, const double* alpha, int L, int K, double min_var,
                    double max_var, double lower, double* var_out, double* es_out, double* m0_out, size_t abi);
+size_t dynamic_distribution_scratch(int dim, int nrows, long long T, int nb);         // cvq_dynamic_distribution.hip
+size_t dynamic_distribution_upload_doubles(long long T);
+int launch_dynamic_distribution(const StaticDev& S, long long T, hipStream_t stream, const double* a,
+                                const double* pi, double* tA, double* tB, double* work, const double* edges,
+                                const double* shared, int nb, double* mass_out, double* m1_out, size_t abi);
 size_t attrib_scratch(int dim, int nrows);                                            // cvq_attrib.hip
 int launch_attrib(const StaticDev& S, long long T, hipStream_t stream, const double* a, const double* pi, double* tA,
                   double* tB, double* part, const double* bounds, const double* var, double lower, double ptf_mean,
@@ -1378,6 +1388,76 @@ double w0_reciprocal(double w0) {
     return (m2 == 0.5 && std::isnormal(1.0 / w0)) ? 1.0 / w0 : 0.0;
 }
 
+// The date records of a per-date call (cvq_dynamic_quantiles, cvq_dynamic_distribution): recs
+// [T][16] in dynamic_pack's layout, each formed as cvq_plan_create forms the plan's own constants,
+// and validated by cvq_plan_create's rules with the date in the message.  A NULL array means the
+// plan's own value on every date.  mean != nullptr: the dates' means too (ptf_mean_t[t], or
+// ptf_mean where that is NULL), each required finite after its date's parameters and weights.
+int dynamic_records(const cvq_plan* p, const double* copula_params_t, const double* weights_t,
+                    const double* ptf_mean_t, double ptf_mean, double* recs, double* mean) {
+    const StaticDev& S = p->S;
+    const long long T = p->T;
+    const int d = S.dim, ncp = p->n_cp;
+    const int kind = S.copula == CVQ_GUMBEL ? (S.survival ? CVQ_GUMBEL_SURVIVAL : CVQ_GUMBEL)
+                   : S.copula == CVQ_PRODFORM ? (S.survival == kFamFrank ? CVQ_FRANK
+                                                 : S.survival == kFamJoe ? CVQ_JOE : CVQ_JOE_SURVIVAL)
+                                              : S.copula;
+    const double own_w[4] = {S.w0, S.w1, S.w2, S.w0_inv};
+    for (long long t = 0; t < T; ++t) {
+        const auto at = [t] { return " at date " + std::to_string(t); };   // built on a failure only
+        CopulaConst cc;
+        cc.theta = S.theta;
+        cc.term1 = S.term1;
+        for (int i = 0; i < 9; ++i) cc.Ri[i] = S.Ri[i];
+        if (copula_params_t) {
+            const double* cp = copula_params_t + (size_t)t * ncp;
+            for (int i = 0; i < ncp; ++i)
+                CVQ_REQUIRE(std::isfinite(cp[i]), CVQ_ERR_INVALID, "a copula parameter must be finite" + at());
+            if (S.copula == CVQ_GUMBEL) {
+                CVQ_REQUIRE(cp[0] >= 1.0, CVQ_ERR_INVALID, "Gumbel theta must be >= 1" + at());
+                CVQ_REQUIRE(cp[0] <= 16.0, CVQ_ERR_UNSUPPORTED, "Gumbel theta must be <= 16" + at());
+            }
+            if (kind == CVQ_FRANK) {
+                CVQ_REQUIRE(cp[0] != 0.0, CVQ_ERR_INVALID, "Frank theta must be > 0" + at());
+                CVQ_REQUIRE(cp[0] > 0.0, CVQ_ERR_UNSUPPORTED, "Frank theta < 0 is not supported" + at());
+                CVQ_REQUIRE(cp[0] <= 32.0, CVQ_ERR_UNSUPPORTED, "Frank theta must be <= 32" + at());
+            }
+            if (kind == CVQ_JOE || kind == CVQ_JOE_SURVIVAL) {
+                CVQ_REQUIRE(cp[0] >= 1.0, CVQ_ERR_INVALID, "Joe theta must be >= 1" + at());
+                CVQ_REQUIRE(cp[0] <= 16.0, CVQ_ERR_UNSUPPORTED, "Joe theta must be <= 16" + at());
+            }
+            if (S.copula == CVQ_STUDENT) {
+                CVQ_REQUIRE(cp[0] > 0.0, CVQ_ERR_INVALID, "nu must be > 0" + at());
+                CVQ_REQUIRE(cp[0] == S.nu, CVQ_ERR_UNSUPPORTED,
+                            "the Student nu is fixed per plan (copula_params_t[t][0] must equal the plan's nu)" + at());
+            }
+            if (S.copula == CVQ_GAUSSIAN || S.copula == CVQ_STUDENT)
+                for (int i = S.copula == CVQ_STUDENT ? 1 : 0; i < ncp; ++i)
+                    CVQ_REQUIRE(std::fabs(cp[i]) < 1.0, CVQ_ERR_INVALID, "a correlation must lie inside (-1, 1)" + at());
+            cc = CopulaConst();
+            const double det = copula_constants(kind, d, cp, &cc);
+            CVQ_REQUIRE(det > 0.0, CVQ_ERR_INVALID, "the correlation matrix is not positive definite" + at());
+        }
+        double w[4] = {own_w[0], own_w[1], own_w[2], own_w[3]};
+        if (weights_t) {
+            const double* wt = weights_t + (size_t)t * d;
+            for (int i = 0; i < d; ++i) CVQ_REQUIRE(std::isfinite(wt[i]), CVQ_ERR_INVALID, "a weight must be finite" + at());
+            CVQ_REQUIRE(wt[0] > 0.0, CVQ_ERR_UNSUPPORTED,
+                        "weights_t[t][0] must be > 0 (the inner-axis division, Q10)" + at());
+            w[0] = wt[0];
+            w[1] = wt[1];
+            w[2] = d == 3 ? wt[2] : 0.0;
+            w[3] = w0_reciprocal(wt[0]);
+        }
+        if (mean) {
+            mean[t] = ptf_mean_t ? ptf_mean_t[t] : ptf_mean;
+            CVQ_REQUIRE(std::isfinite(mean[t]), CVQ_ERR_INVALID, "ptf_mean must be finite" + at());
+        }
+        dynamic_pack(recs, t, cc.theta, cc.term1, cc.Ri, w);
+    }
+    return CVQ_OK;
+}
+
 // A pinned host buffer of at least `need` doubles whose last upload has completed (a new one
 // where every buffer is still in flight or too small).
 int dyn_stage_take(cvq_plan* p, size_t need, cvq_plan::DynStage** out) {
@@ -1424,6 +1504,36 @@ int run_dynamic(cvq_plan* p, const cvq_solve_args& a, int K, const double* up, c
     CVQ_HIP_CHECK(hipEventRecord(stage->done, p->stream));
     return launch_dynamic(p->S, p->T, p->stream, p->in_a, p->in_pi, p->d_mA, p->d_mB, p->d_dwork, levels, L, K,
                           a.min_var, a.max_var, a.lower, var, es, m0, kernel_abi_key());
+}
+
+// Per-date-record distribution: the moments' table scratch + a work buffer of their own whose
+// head takes the records, `extra` doubles behind the partial sums (the host mode's staging).
+int ensure_dynamic_distribution(cvq_plan* p, int nb, size_t extra) {
+    int rc = ensure_moments(p);
+    if (rc) return rc;
+    const size_t need = dynamic_distribution_scratch(p->S.dim, p->S.nrows, p->T, nb) + extra;
+    if (need > p->capDynDist) {
+        p->capDynDist = 0;
+        if ((rc = dev_alloc(&p->d_ddist, need))) return rc;
+        p->capDynDist = need;
+    }
+    return CVQ_OK;
+}
+
+// recs: host [T][16]; copied to a pinned buffer before returning, uploaded in stream order.
+// Timed with the tail moments (kind 5), as cvq_distribution.
+int run_dynamic_distribution(cvq_plan* p, const double* recs, const double* edges, const double* shared, int nb,
+                             double* mass, double* m1) {
+    const size_t nup = dynamic_distribution_upload_doubles(p->T);
+    cvq_plan::DynStage* stage = nullptr;
+    int rc = dyn_stage_take(p, nup, &stage);
+    if (rc) return rc;
+    std::memcpy(stage->h, recs, nup * sizeof(double));
+    TimedScope ts(p, TK_MOMENTS);
+    CVQ_HIP_CHECK(hipMemcpyAsync(p->d_ddist, stage->h, nup * sizeof(double), hipMemcpyHostToDevice, p->stream));
+    CVQ_HIP_CHECK(hipEventRecord(stage->done, p->stream));
+    return launch_dynamic_distribution(p->S, p->T, p->stream, p->in_a, p->in_pi, p->d_mA, p->d_mB, p->d_ddist, edges,
+                                       shared, nb, mass, m1, kernel_abi_key());
 }
 
 }  // namespace
@@ -1705,7 +1815,7 @@ int32_t cvq_plan_destroy(cvq_plan* p) {
                     (void*)p->d_cutfix, (void*)p->d_kcut, (void*)p->d_fpair, (void*)p->d_ccount, (void*)p->d_tlist, (void*)p->d_tvs, (void*)p->d_defer, (void*)p->d_vstar, (void*)p->d_bucket, (void*)p->d_sidx, (void*)p->d_svs,
                     (void*)p->d_tree, (void*)p->d_pass,
                     (void*)p->d_pidx, (void*)p->d_pvs, (void*)p->d_cwork, (void*)p->d_pwork, (void*)p->d_dwork,
-                    (void*)p->d_dist})
+                    (void*)p->d_dist, (void*)p->d_ddist})
         if (b) (void)hipFree(b);
     for (auto& st : p->dyn_stage) { (void)hipEventDestroy(st.done); (void)hipHostFree(st.h); }
     if (p->own_stream) (void)hipStreamDestroy(p->own_stream);
@@ -2176,67 +2286,12 @@ int32_t cvq_dynamic_quantiles(cvq_plan* p, const cvq_solve_args* a, const double
     CVQ_REQUIRE(steps <= (double)kMaxIters, CVQ_ERR_UNSUPPORTED, "bisection needs more than 62 iterations");
     const int K = steps > 0.0 ? (int)steps : 0;
     CVQ_REQUIRE(p->T > 0, CVQ_ERR_STATE, "cvq_set_dates must be called first");
-    const StaticDev& S = p->S;
     const long long T = p->T;
-    const int d = S.dim, ncp = p->n_cp;
-    const int kind = S.copula == CVQ_GUMBEL ? (S.survival ? CVQ_GUMBEL_SURVIVAL : CVQ_GUMBEL)
-                   : S.copula == CVQ_PRODFORM ? (S.survival == kFamFrank ? CVQ_FRANK
-                                                 : S.survival == kFamJoe ? CVQ_JOE : CVQ_JOE_SURVIVAL)
-                                              : S.copula;
     // the date records, each formed as cvq_plan_create forms the plan's own constants
     std::vector<double> up(dynamic_upload_doubles(T));
-    double* mean = up.data() + dynamic_mean_offset(T);
-    const double own_w[4] = {S.w0, S.w1, S.w2, S.w0_inv};
-    for (long long t = 0; t < T; ++t) {
-        const auto at = [t] { return " at date " + std::to_string(t); };   // built on a failure only
-        CopulaConst cc;
-        cc.theta = S.theta;
-        cc.term1 = S.term1;
-        for (int i = 0; i < 9; ++i) cc.Ri[i] = S.Ri[i];
-        if (copula_params_t) {
-            const double* cp = copula_params_t + (size_t)t * ncp;
-            for (int i = 0; i < ncp; ++i)
-                CVQ_REQUIRE(std::isfinite(cp[i]), CVQ_ERR_INVALID, "a copula parameter must be finite" + at());
-            if (S.copula == CVQ_GUMBEL) {
-                CVQ_REQUIRE(cp[0] >= 1.0, CVQ_ERR_INVALID, "Gumbel theta must be >= 1" + at());
-                CVQ_REQUIRE(cp[0] <= 16.0, CVQ_ERR_UNSUPPORTED, "Gumbel theta must be <= 16" + at());
-            }
-            if (kind == CVQ_FRANK) {
-                CVQ_REQUIRE(cp[0] != 0.0, CVQ_ERR_INVALID, "Frank theta must be > 0" + at());
-                CVQ_REQUIRE(cp[0] > 0.0, CVQ_ERR_UNSUPPORTED, "Frank theta < 0 is not supported" + at());
-                CVQ_REQUIRE(cp[0] <= 32.0, CVQ_ERR_UNSUPPORTED, "Frank theta must be <= 32" + at());
-            }
-            if (kind == CVQ_JOE || kind == CVQ_JOE_SURVIVAL) {
-                CVQ_REQUIRE(cp[0] >= 1.0, CVQ_ERR_INVALID, "Joe theta must be >= 1" + at());
-                CVQ_REQUIRE(cp[0] <= 16.0, CVQ_ERR_UNSUPPORTED, "Joe theta must be <= 16" + at());
-            }
-            if (S.copula == CVQ_STUDENT) {
-                CVQ_REQUIRE(cp[0] > 0.0, CVQ_ERR_INVALID, "nu must be > 0" + at());
-                CVQ_REQUIRE(cp[0] == S.nu, CVQ_ERR_UNSUPPORTED,
-                            "the Student nu is fixed per plan (copula_params_t[t][0] must equal the plan's nu)" + at());
-            }
-            if (S.copula == CVQ_GAUSSIAN || S.copula == CVQ_STUDENT)
-                for (int i = S.copula == CVQ_STUDENT ? 1 : 0; i < ncp; ++i)
-                    CVQ_REQUIRE(std::fabs(cp[i]) < 1.0, CVQ_ERR_INVALID, "a correlation must lie inside (-1, 1)" + at());
-            cc = CopulaConst();
-            const double det = copula_constants(kind, d, cp, &cc);
-            CVQ_REQUIRE(det > 0.0, CVQ_ERR_INVALID, "the correlation matrix is not positive definite" + at());
-        }
-        double w[4] = {own_w[0], own_w[1], own_w[2], own_w[3]};
-        if (weights_t) {
-            const double* wt = weights_t + (size_t)t * d;
-            for (int i = 0; i < d; ++i) CVQ_REQUIRE(std::isfinite(wt[i]), CVQ_ERR_INVALID, "a weight must be finite" + at());
-            CVQ_REQUIRE(wt[0] > 0.0, CVQ_ERR_UNSUPPORTED,
-                        "weights_t[t][0] must be > 0 (the inner-axis division, Q10)" + at());
-            w[0] = wt[0];
-            w[1] = wt[1];
-            w[2] = d == 3 ? wt[2] : 0.0;
-            w[3] = w0_reciprocal(wt[0]);
-        }
-        mean[t] = ptf_mean_t ? ptf_mean_t[t] : a->ptf_mean;
-        CVQ_REQUIRE(std::isfinite(mean[t]), CVQ_ERR_INVALID, "ptf_mean must be finite" + at());
-        dynamic_pack(up.data(), t, cc.theta, cc.term1, cc.Ri, w);
-    }
+    if (int rc = dynamic_records(p, copula_params_t, weights_t, ptf_mean_t, a->ptf_mean, up.data(),
+                                 up.data() + dynamic_mean_offset(T)))
+        return rc;
     if (mem == CVQ_MEM_DEVICE) return run_dynamic(p, *a, K, up.data(), levels, n_levels, var_out, es_out, m0_out);
     const long long TL = T * n_levels;
     int rc = ensure_io(p, 3 * TL);
@@ -2259,6 +2314,43 @@ int32_t cvq_dynamic_scratch(const cvq_plan* p, int32_t n_levels, int64_t* bytes)
     CVQ_REQUIRE(n_levels >= 1 && n_levels <= CVQ_MAX_LEVELS, CVQ_ERR_INVALID, "n_levels must be in [1, CVQ_MAX_LEVELS]");
     CVQ_REQUIRE(p->T > 0, CVQ_ERR_STATE, "cvq_set_dates must be called first");
     *bytes = (int64_t)(dynamic_scratch(p->S.dim, p->S.nrows, p->T, n_levels) * sizeof(double));
+    return CVQ_OK;
+}
+
+int32_t cvq_dynamic_distribution(cvq_plan* p, const double* copula_params_t, const double* weights_t,
+                                 const double* edges, int32_t n_bins, int32_t per_date, double* mass_out,
+                                 double* m1_out, int32_t mem) {
+    cvq::DeviceScope device_scope;                 // the caller's current device, restored on return
+    // cvq_distribution's checks in its order, then the dates' values: all on the host before any
+    // device work
+    CVQ_REQUIRE(edges != nullptr && mass_out != nullptr, CVQ_ERR_INVALID, "NULL argument");
+    CVQ_REQUIRE(n_bins >= 1 && n_bins <= CVQ_MAX_BINS, CVQ_ERR_INVALID, "n_bins must be in [1, CVQ_MAX_BINS]");
+    CVQ_REQUIRE(per_date == 0 || per_date == 1, CVQ_ERR_INVALID, "per_date must be 0 or 1");
+    CVQ_REQUIRE(p != nullptr, CVQ_ERR_INVALID, "plan is NULL");
+    CVQ_REQUIRE(p->T > 0, CVQ_ERR_STATE, "cvq_set_dates must be called first");
+    int rc = distribution_check(p->S);
+    if (rc) return rc;
+    const long long T = p->T;
+    // the date records, each formed as cvq_plan_create forms the plan's own constants
+    std::vector<double> recs(dynamic_distribution_upload_doubles(T));
+    if ((rc = dynamic_records(p, copula_params_t, weights_t, nullptr, 0.0, recs.data(), nullptr))) return rc;
+    CVQ_HIP_CHECK(hipSetDevice(p->device));
+    const size_t TB = (size_t)T * n_bins, TE = (size_t)T * (n_bins + 1);
+    if (mem == CVQ_MEM_DEVICE) {
+        if ((rc = ensure_dynamic_distribution(p, n_bins, 0))) return rc;
+        return run_dynamic_distribution(p, recs.data(), per_date ? edges : nullptr, edges, n_bins, mass_out, m1_out);
+    }
+    if ((rc = ensure_dynamic_distribution(p, n_bins, TE + 2 * TB))) return rc;
+    double* d_edges = p->d_ddist + dynamic_distribution_scratch(p->S.dim, p->S.nrows, T, n_bins);
+    double* d_mass = d_edges + TE;
+    double* d_m1 = m1_out ? d_mass + TB : nullptr;
+    if (per_date)
+        CVQ_HIP_CHECK(hipMemcpyAsync(d_edges, edges, TE * sizeof(double), hipMemcpyHostToDevice, p->stream));
+    if ((rc = run_dynamic_distribution(p, recs.data(), per_date ? d_edges : nullptr, edges, n_bins, d_mass, d_m1)))
+        return rc;
+    CVQ_HIP_CHECK(hipMemcpyAsync(mass_out, d_mass, TB * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    if (m1_out) CVQ_HIP_CHECK(hipMemcpyAsync(m1_out, d_m1, TB * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    CVQ_HIP_CHECK(hipStreamSynchronize(p->stream));
     return CVQ_OK;
 }
 

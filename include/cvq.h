@@ -130,7 +130,7 @@ int32_t cvq_plan_info(const cvq_plan* plan, int64_t* reach_nodes, int32_t* rows)
  * live roofline).  kind: 0 tables, 1 joint-mass/prefix, 2 solve, 3 finalize,
  * 4 slab, 5 tail moments (cvq_slab_moments / cvq_expected_shortfall and the axis moments
  * cvq_slab_axis_moments / cvq_es_contributions: their tables,
- * partial sums and finish together; cvq_distribution likewise), 6 exact quantiles (cvq_quantiles and its conditional,
+ * partial sums and finish together; cvq_distribution and cvq_dynamic_distribution likewise), 6 exact quantiles (cvq_quantiles and its conditional,
  * batched-weights and per-date-record forms: their tables, passes and updates together).
  * cvq_plan_timing(mask) times the kinds whose bit (1 << kind) is
  * set (0 = off, 0x7F = all) and clears previous records. */
@@ -393,6 +393,34 @@ int32_t cvq_dynamic_quantiles(cvq_plan* plan, const cvq_solve_args* args, const 
 /* Bytes of device scratch one cvq_dynamic_quantiles call of n_levels levels takes on the plan's
  * current batch (the date records included). */
 int32_t cvq_dynamic_scratch(const cvq_plan* plan, int32_t n_levels, int64_t* bytes);
+
+/* No reference counterpart.  cvq_distribution under per-date copula parameters and weights on one
+ * plan: the predictive distribution of the forecast that cvq_dynamic_quantiles produces (a rolling
+ * refit on a drifting book), so that forecast can be backtested (PIT, coverage, scoring).
+ *   mass_out[t][:] and m1_out[t][:] are what cvq_distribution returns, bit for bit, on a plan that
+ *   differs from this one only in cvq_static.copula_params = copula_params_t[t] and
+ *   cvq_static.weights = weights_t[t], given date t alone or date t in any batch,
+ * cvq_plan_create's reciprocal rule for weights[0] included.  copula_params_t
+ * [T][n_copula_params] and weights_t [T][dim] follow cvq_dynamic_quantiles' conventions: host
+ * memory whatever `mem` says, not needed after the call; a NULL array means the plan's own value
+ * on every date, and with both NULL the call is cvq_distribution, bit for bit.  Fixed per plan:
+ * the copula kind (with the survival / family code) and the Student nu.
+ * edges, n_bins, per_date, mass_out, m1_out and mem are cvq_distribution's: edges host
+ * [n_bins + 1] serving every date (per_date == 0), or [T][n_bins + 1] host|device (per_date == 1).
+ * Edges are centred levels: there is no mean argument, a caller with a per-date mean subtracts it
+ * from each date's ladder.  Every property of cvq_distribution carries over: each bin stands
+ * alone, a NaN, repeated or descending pair of edges is exactly (0, 0), +-inf edges are valid, a
+ * bin depends on its own two edges and its date's inputs and record alone, results are
+ * bit-identical between runs (fixed-order sums, no atomics).  Runs on every strategy with no
+ * v_cap limit, on lazily sized scratch of its own; the plan's solve state is untouched.
+ * CVQ_MEM_DEVICE is stream-ordered without a host synchronisation.  Timed under kind 5.
+ * cvq_distribution's argument checks come first, in its order and with its codes; then the
+ * per-date values by cvq_dynamic_quantiles' rules, codes and "at date <t>" wording (one helper
+ * serves both entry points).  All of it happens on the host before any device work; a failure
+ * leaves the outputs unwritten. */
+int32_t cvq_dynamic_distribution(cvq_plan* plan, const double* copula_params_t, const double* weights_t,
+                                 const double* edges, int32_t n_bins, int32_t per_date,
+                                 double* mass_out, double* m1_out, int32_t mem);
 
 /* Drop-in for ValueAtRiskCalcualtion.calc_var (calc_var_class.py:95-177 +
  * bisection_algorithm :250-309), quirks Q1-Q4 reproduced.  var_out [T];
