@@ -241,6 +241,8 @@ def calc_var(compute_integral, T, ptf_mean, obj_var=0.05, first_guess=-3, second
         b = np.where(upper_stack[:, None], np.column_stack((lo, mid)), np.column_stack((mid, hi)))
         mid_result = compute_integral(b)
         rc = adjust_integral(mid_result, prev_result, b, prev_upper)
+        if trace is not None:                                # (prev, slab, F) of every level: the decisions' margins
+            trace.setdefault("steps", []).append((prev_result.copy(), mid_result.copy(), rc.copy()))
         if np.all(rc == 0):                                                            # Q4
             broke = True
             break

@@ -90,6 +90,16 @@ TIERS = {
     ("cond", "gaussian", False): "precise", ("cond", "plackett", False): "precise",
     ("port", "student", False): "precise", ("port", "student", True): "precise",
     ("port", "gaussian", False): "precise", ("port", "plackett", False): "precise",
+    # the predictive distribution and the per-date-record passes (tests/test_q_sweep_gpu.py): their own copies of
+    # the slab-row core again -- "dist": k_dist_pass, make_row / outer_B / node_value at
+    # cvq_distribution_kernels.h:102-103 and :132, and k_dyn_dist_pass, cvq_dynamic_distribution_kernels.h:110-111
+    # and :141; "dyn": k_dyn_pass, cvq_dynamic_kernels.h:183-184 and :191 -- node_value, whatever the plan's
+    # strategy and whether the date's parameters are the plan's or a record's
+    ("dist", "student", False): "precise", ("dist", "student", True): "precise",
+    ("dist", "gaussian", False): "precise", ("dist", "plackett", False): "precise",
+    ("dyn", "student", False): "precise", ("dyn", "student", True): "precise",
+    ("dyn", "gaussian", False): "precise", ("dyn", "plackett", False): "precise",
+    ("dist", "gumbel", False): "precise", ("dyn", "gumbel", False): "precise",
     # the Gumbel kinds (both under "gumbel"; SORTED only, cvq_plan.hip:1348): a SORTED slab of rank-1 dates
     # takes the record path, node_fast at cvq_sorted_kernels.h:578-594 -- log_node / exp_node inside, the outer
     # exponential exp2_node7; dates whose pi_t is not rank 1 take node_generic -> node_value (:599-), as do the
@@ -235,6 +245,11 @@ def test_tier_table_is_complete():
     for copula, general in (("student", False), ("student", True), ("gaussian", False), ("plackett", False),
                             ("gumbel", False)):
         assert TIERS[("cond", copula, general)] == TIERS[("port", copula, general)] == TIERS[("moments", copula, general)]
+        # so do the distribution and per-date-record passes (tests/test_q_sweep_gpu.py)
+        assert TIERS[("dist", copula, general)] == TIERS[("dyn", copula, general)] == TIERS[("moments", copula, general)]
+    for case in CASES:
+        for fam in ("dist", "dyn", "cond", "port"):
+            assert bar_of(fam, *case[1:]) == bar_of("moments", *case[1:])
     assert TIERS[("sorted", "gumbel", False)] == "fast" and TIERS[("sorted-generic", "gumbel", False)] == "precise"
     assert not any(fam in ("prefix", "direct") and copula == "gumbel" for fam, copula, _ in TIERS)
     assert all(t in ("precise", "fast") for t in TIERS.values())
