@@ -123,6 +123,8 @@ def _declare(lib: C.CDLL) -> None:
         "cvq_garch_loglik_pq": (i32, [i32, i32, i32, v, i64, v, i64, v, i32]),
         "cvq_ukf_loglik": (i32, [i32, v, i64, v, i64, v, i32]),
         "cvq_ukf_filter": (i32, [i32, v, i64, v, i32, i64, v, v, i32]),
+        "cvq_gas_loglik": (i32, [i32, i32, i32, i32, d, v, i64, v, i64, v, i32]),
+        "cvq_gas_path": (i32, [i32, i32, i32, i32, d, v, v, i64, v, v, i32]),
         "cvq_special": (i32, [i32, i32, d, v, i64, v, i32]),
     }
     for name, (res, args) in sig.items():

@@ -1,8 +1,9 @@
 """Per-date inputs of QuadraturePlan.dynamic_quantiles: buy-and-hold weights that drift with the
 realised returns, the out-of-sample probability integral transforms of the forecast marginals,
-and copula parameters refitted on a rolling window.  numpy / scipy only (the Student and Gaussian
-fits take their quantiles from the device unless a host function is passed, as the optimisers of
-optim/copula_fit.py do); no kernels of its own.
+copula parameters refitted on a rolling window, and the path of a score-driven copula recursion
+fitted once (gas_copula_params; its likelihoods and its filter are the kernels of csrc/cvq_gas.hip).
+Otherwise numpy / scipy only (the Student and Gaussian fits take their quantiles from the device
+unless a host function is passed, as the optimisers of optim/copula_fit.py do).
 
 Nothing here looks ahead: the weights and the parameters of out-of-sample date t are functions of
 the rows before t alone.
@@ -197,3 +198,48 @@ def rolling_copula_params(copula: str, in_sample_marginals, in_sample_densities,
         out.append(prev)
     n_par = len(out[0]) if out else (0 if static is None else static.size)
     return np.array(out, dtype=np.float64).reshape(T, n_par), info
+
+
+# ---------------------------------------------------------------------- score-driven copula path
+def gas_copula_params(copula: str, in_sample_marginals, oos_u, static_params, fit=None, device: int = 0,
+                      in_sample_densities=None, path: Optional[Callable] = None) -> Tuple[np.ndarray, dict]:
+    """(params (T, n_copula_params), info): the copula parameters of every out-of-sample date, in
+    cvq_static.copula_params' packing (Student: [nu, rho_t]), from the score-driven recursion of
+    optim.copula_fit.GasCopulaOptimizer (DESIGN.md §4 "Score-driven copula").
+
+    The three recursion parameters are fitted once, on the in-sample rows only; the filter then runs
+    once over [in-sample rows, then out-of-sample rows] and rows n_in ... n_in + T - 1 of its path are
+    returned: the parameter of out-of-sample date t is a function of the rows before it alone.
+    static_params (the static fit, same packing) gives the Student nu -- fixed, the plan's -- and the
+    level the search starts from.  Marginals are clamped to [2^-53, 1 - 2^-53] as the optimiser does.
+    fit: None (GasCopulaOptimizer on the device), a dict with "omega", "alpha", "beta" (a fit made
+    elsewhere), or a function (copula, u_in, densities, nu, static_theta, device) -> such a dict.
+    path: the filter, (u, params) -> (theta (N + 1,), logc (N,)); default engine.gas_path.
+    in_sample_densities only shifts the reported likelihoods (default: ones).
+    info: "fit" (the fit dict) and "in_sample_path" (theta_0 ... theta_{n_in - 1})."""
+    from .optim import copula_fit as F
+    if copula not in COPULAS:
+        raise ValueError(f"copula must be one of {COPULAS}")
+    um, uo = np.asarray(in_sample_marginals, dtype=np.float64), np.asarray(oos_u, dtype=np.float64)
+    if um.ndim != 2 or uo.ndim != 2 or um.shape[1] != uo.shape[1]:
+        raise ValueError("marginals must be (N, dim) in-sample and (T, dim) out-of-sample")
+    static = np.atleast_1d(np.asarray(static_params, dtype=np.float64))
+    if um.shape[1] != 2 and copula in ("gaussian", "student", "plackett"):
+        raise ValueError(f"the score-driven {copula} copula is built for 2 assets")
+    nu = float(static[0]) if copula == "student" else None
+    dens = np.ones_like(um) if in_sample_densities is None else np.asarray(in_sample_densities, dtype=np.float64)
+    if fit is None:
+        fit = F.GasCopulaOptimizer(um, dens, copula, nu=nu, static_theta=static[-1], device=device).optimize()
+    elif callable(fit):
+        fit = fit(copula, um, dens, nu, float(static[-1]), device)
+    prm = np.array([fit["omega"], fit["alpha"], fit["beta"]], dtype=np.float64)
+    edge = F.GasCopulaOptimizer.EDGE
+    rows = np.clip(np.vstack((um, uo)), edge, 1.0 - edge)
+    if path is None:
+        from . import engine
+        path = lambda u, p: engine.gas_path(u, copula, p, nu=nu, device=device)      # noqa: E731
+    theta, _ = path(rows, prm)
+    n_in, T = um.shape[0], uo.shape[0]
+    th = np.asarray(theta, dtype=np.float64)[n_in:n_in + T]
+    out = np.column_stack((np.full(T, nu), th)) if copula == "student" else th.reshape(T, 1)
+    return np.ascontiguousarray(out), {"fit": fit, "in_sample_path": np.asarray(theta, dtype=np.float64)[:n_in]}

@@ -972,3 +972,42 @@ def ukf_filter(returns, params, device: int = 0):
     N.check(N.lib().cvq_ukf_filter(device, N.ptr(p), B, N.ptr(r), per, n, N.ptr(ll), N.ptr(states), N.MEM_HOST),
             "cvq_ukf_filter")
     return ll, np.ascontiguousarray(states.T)
+
+
+def _gas_args(u, copula: str, nu, survival: bool):
+    if copula not in N.COPULA_KIND:
+        raise ValueError(f"copula must be one of {sorted(N.COPULA_KIND)}")
+    uu = N.f64(u)
+    if uu.ndim != 2:
+        raise ValueError("u must be (N, dim)")
+    if copula == "student" and nu is None:
+        raise ValueError("the score-driven Student copula needs nu (it stays fixed)")
+    return uu, N.COPULA_KIND[copula], int(bool(survival)), float(0.0 if nu is None else nu)
+
+
+def gas_loglik(u, copula: str, params, nu=None, survival: bool = False, device: int = 0) -> np.ndarray:
+    """Score-driven copula log-likelihoods (cvq_gas_loglik): u (N, dim) in (0, 1), params (B, 3) rows
+    (omega, alpha, beta) -> (B,), all rows in one launch; NaN for a row with |beta| >= 1, a
+    non-finite parameter or a recursion that leaves the finite numbers.  copula: a name of
+    _native.COPULA_KIND ("gumbel_survival" / "joe_survival", or survival=True with "gumbel" / "joe")."""
+    uu, kind, surv, nuv = _gas_args(u, copula, nu, survival)
+    pp = N.f64(np.atleast_2d(params))
+    if pp.shape[1] != 3:
+        raise ValueError(f"parameter rows are (omega, alpha, beta), got {pp.shape[1]} entries")
+    out = np.empty(pp.shape[0])
+    N.check(N.lib().cvq_gas_loglik(device, kind, surv, uu.shape[1], nuv, N.ptr(pp), pp.shape[0], N.ptr(uu),
+                                   uu.shape[0], N.ptr(out), N.MEM_HOST), "cvq_gas_loglik")
+    return out
+
+
+def gas_path(u, copula: str, params, nu=None, survival: bool = False, device: int = 0):
+    """The filtered path of one candidate (cvq_gas_path): (theta (N + 1,), logc (N,)).  theta[t] uses
+    the rows before t only; theta[N] is the one-step-ahead forecast."""
+    uu, kind, surv, nuv = _gas_args(u, copula, nu, survival)
+    pp = N.f64(params).ravel()
+    if pp.size != 3:
+        raise ValueError("params is one (omega, alpha, beta)")
+    theta, logc = np.empty(uu.shape[0] + 1), np.empty(uu.shape[0])
+    N.check(N.lib().cvq_gas_path(device, kind, surv, uu.shape[1], nuv, N.ptr(pp), N.ptr(uu), uu.shape[0],
+                                 N.ptr(theta), N.ptr(logc), N.MEM_HOST), "cvq_gas_path")
+    return theta, logc

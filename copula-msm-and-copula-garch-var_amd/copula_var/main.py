@@ -12,7 +12,7 @@ Then, per estimation type, the pipeline main.py runs: factory -> ValueAtRiskCalc
 The VaR series (one column per estimation type) and the equal-weight portfolio
 returns go to --out; --plot saves main.py's plot_var_and_returns figure to a file.
 --backtest tests each VaR series against those portfolio returns (copula_var.backtest), the
-dynamic ones (--rolling-copula, --drift-weights) under their own per-date predictive distribution.
+dynamic ones (--rolling-copula, --gas-copula, --drift-weights) under their own per-date predictive distribution.
 """
 from __future__ import annotations
 
@@ -94,6 +94,11 @@ def build_parser() -> argparse.ArgumentParser:
                          "(in-sample rows, then the realised out-of-sample rows; a Student nu stays fixed): "
                          "dvar_<estimation>_<level> / des_<estimation>_<level> columns in --out, the parameter "
                          "path in dparam_<estimation>_<k>")
+    ap.add_argument("--gas-copula", action="store_true",
+                    help="as --rolling-copula, but the parameter path comes from a score-driven (GAS) recursion: "
+                         "three parameters (omega, alpha, beta) fitted once on the in-sample marginals on the "
+                         "device, then filtered through the realised out-of-sample rows; the same dvar / des / "
+                         "dparam columns.  Needs --exact-levels; not with --rolling-copula")
     ap.add_argument("--refit-every", type=int, default=21, metavar="STEP",
                     help="out-of-sample dates between two refits of --rolling-copula (default 21)")
     ap.add_argument("--drift-weights", action="store_true",
@@ -122,9 +127,13 @@ def main(argv=None) -> int:
         raise SystemExit(f"--covar {a.covar}: not one of --tickers")
     if a.weight_grid is not None and a.weight_grid < 1:
         raise SystemExit("--weight-grid: STEPS must be >= 1")
-    dynamic_on = a.rolling_copula is not None or a.drift_weights
+    dynamic_on = a.rolling_copula is not None or a.drift_weights or a.gas_copula
     if dynamic_on and not a.exact_levels:
-        raise SystemExit("--rolling-copula, --refit-every and --drift-weights need --exact-levels")
+        raise SystemExit("--rolling-copula, --gas-copula, --refit-every and --drift-weights need --exact-levels")
+    if a.gas_copula and a.rolling_copula is not None:
+        raise SystemExit("--gas-copula and --rolling-copula are two producers of one parameter path: choose one")
+    if a.gas_copula and len(a.tickers) != 2 and a.copula in ("gaussian", "student", "plackett"):
+        raise SystemExit(f"--gas-copula: the score-driven {a.copula} copula is built for 2 assets")
     if a.refit_every != 21 and a.rolling_copula is None:
         raise SystemExit("--refit-every needs --rolling-copula")
     if a.rolling_copula is not None and a.rolling_copula < 2:
@@ -178,6 +187,14 @@ def main(argv=None) -> int:
                 path, info = run.rolling_copula_params(a.rolling_copula, a.refit_every)
                 print(f"{est}/{a.copula}: rolling copula, window {a.rolling_copula}: {len(info['refits'])} refits, "
                       f"{len(info['failed'])} failed; parameters from "
+                      + ", ".join(f"{v:.4f}" for v in path[0]) + " to " + ", ".join(f"{v:.4f}" for v in path[-1]),
+                      file=sys.stderr)
+            if a.gas_copula:
+                path, info = run.gas_copula_params()
+                fit = info["fit"]
+                print(f"{est}/{a.copula}: score-driven copula: omega {fit['omega']:.6f}, alpha {fit['alpha']:.6f}, "
+                      f"beta {fit['beta']:.6f}; NLL {fit['nll']:.4f} (static {fit['static_nll']:.4f}), "
+                      f"{fit['launches']} launches; parameters from "
                       + ", ".join(f"{v:.4f}" for v in path[0]) + " to " + ", ".join(f"{v:.4f}" for v in path[-1]),
                       file=sys.stderr)
             wt = None

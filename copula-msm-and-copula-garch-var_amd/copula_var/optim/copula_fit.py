@@ -306,3 +306,142 @@ class JoeCopulaOptimizer(_OneParameterIFM):
 
     def _log_density(self, th):
         return joe_log_density(self._u, th, self.survival)
+
+
+# ---------------------------------------------------------------------- score-driven copula
+GAS_FAMILY = {"gaussian": "gaussian", "student": "student", "plackett": "plackett", "gumbel": "gumbel",
+              "gumbel_survival": "gumbel", "frank": "frank", "joe": "joe", "joe_survival": "joe"}
+GAS_RANGE = {"gaussian": (-0.99, 0.99), "student": (-0.99, 0.99), "plackett": (0.1, 1000.0),
+             "gumbel": (1.0001, 16.0), "joe": (1.0001, 16.0), "frank": (1e-3, 32.0)}
+
+
+def gas_link(copula, f):
+    """The bounded sigmoid link of cvq_gas_loglik / cvq_gas_path (include/cvq.h), float64."""
+    fam = GAS_FAMILY[copula]
+    sg = 1.0 / (1.0 + np.exp(-np.asarray(f, dtype=np.float64)))
+    if fam in ("gaussian", "student"):
+        return 0.99 * (2.0 * sg - 1.0)
+    if fam == "plackett":
+        return 0.1 * 10.0 ** (4.0 * sg)
+    lo, hi = GAS_RANGE[fam]
+    return lo + (hi - lo) * sg
+
+
+def gas_link_inverse(copula, theta):
+    """f with gas_link(copula, f) = theta; theta is first moved inside the link's open range."""
+    fam = GAS_FAMILY[copula]
+    lo, hi = GAS_RANGE[fam]
+    th = float(theta)
+    if fam in ("gaussian", "student"):
+        sg = (th / 0.99 + 1.0) / 2.0
+    elif fam == "plackett":
+        sg = np.log10(max(th, lo) / 0.1) / 4.0
+    else:
+        sg = (th - lo) / (hi - lo)
+    sg = min(max(float(sg), 1e-9), 1.0 - 1e-9)
+    return float(np.log(sg) - np.log1p(-sg))
+
+
+class GasCopulaOptimizer(_IFM):
+    """Fit of the score-driven copula recursion (DESIGN.md §4 "Score-driven copula"; cvq_gas_loglik):
+    the three parameters (omega, alpha, beta) of
+        f_{t+1} = clamp(omega + beta f_t + alpha s_t, -40, 40),   theta_t = link(f_t),
+    by maximum likelihood on the in-sample marginals, every likelihood on the device and every
+    optimiser step one launch.
+
+    copula: a name of _native.COPULA_KIND; nu: the Student degrees of freedom (fixed: the plan's).
+    static_theta: the static fit's parameter (rho or theta); None runs the existing static optimiser
+    (copula_var.dynamic.fit_copula).  loglik(rows (B, 3)) -> LL (B,): default the device kernel; tests
+    pass a CPU restatement, as GarchOptimizer allows.  The marginals are clamped to
+    [2^-53, 1 - 2^-53], as the Archimedean optimisers do (GumbelCopulaOptimizer's note).
+
+    optimize(): the 4 x 4 grid beta in BETAS, alpha in ALPHAS, omega = f_bar (1 - beta) with
+    f_bar = link^-1(static theta) in ONE launch; the best N_REFINE starts refined by L-BFGS-B
+    (alpha in [0, 4], beta in [0, 0.999], omega free) whose objective and central-difference gradient
+    come from one 7-row launch per step.  Rows with |beta| >= 1, non-finite rows and NaN
+    likelihoods score 1e10; the first two kinds are never launched.  The grid holds alpha = 0,
+    beta = 0 -- the static model -- so nll <= static_nll."""
+
+    EDGE = 2.0 ** -53
+    BETAS = (0.0, 0.5, 0.9, 0.97)
+    ALPHAS = (0.0, 0.02, 0.1, 0.4)
+    BOUNDS = ((None, None), (0.0, 4.0), (0.0, 0.999))
+    N_REFINE = 3
+    STEP = 1e-5
+
+    def __init__(self, marginals, densities, copula, nu=None, static_theta=None, device: int = 0,
+                 loglik: Optional[Callable] = None, tol=1e-9, max_iter=200):
+        super().__init__(marginals, densities, tol, max_iter, device)
+        if copula not in GAS_FAMILY:
+            raise ValueError(f"copula must be one of {sorted(GAS_FAMILY)}")
+        fam = GAS_FAMILY[copula]
+        if self.dim not in (2, 3) or (self.dim == 3 and fam in ("gaussian", "student", "plackett")):
+            raise ValueError(f"the score-driven {copula} copula is not built for {self.dim} marginals")
+        if fam == "student" and nu is None:
+            raise ValueError("the score-driven Student copula needs nu (it stays fixed)")
+        self.copula, self.nu = copula, None if nu is None else float(nu)
+        self._u = np.clip(self.marginals, self.EDGE, 1.0 - self.EDGE)      # NaN stays NaN
+        self.static_theta = static_theta
+        self._loglik = loglik or self._device_loglik
+        self.evaluations = 0
+
+    def _device_loglik(self, rows):
+        from .. import engine
+        return engine.gas_loglik(self._u, self.copula, rows, nu=self.nu, device=self.device)
+
+    def negative_log_likelihoods(self, rows) -> np.ndarray:
+        """rows (B, 3) -> NLL (B,), the sum of the log marginal densities included; one launch for
+        the rows that can be launched, 1e10 for the others and for NaN likelihoods."""
+        rows = np.atleast_2d(np.asarray(rows, dtype=np.float64))
+        out = np.full(rows.shape[0], 1e10)
+        good = np.all(np.isfinite(rows), axis=1) & (np.abs(rows[:, 2]) < 1.0)
+        if np.any(good):
+            ll = np.asarray(self._loglik(np.ascontiguousarray(rows[good])), dtype=np.float64)
+            self.launches += 1
+            self.evaluations += int(np.sum(good))
+            nll = -(self._log_dens + ll)
+            out[good] = np.where(np.isfinite(nll), nll, 1e10)
+        return out
+
+    def _static_theta(self):
+        if self.static_theta is not None:
+            return float(np.asarray(self.static_theta, dtype=np.float64).reshape(-1)[-1])
+        from ..dynamic import fit_copula
+        got, _ = fit_copula(self.copula, self._u, self.densities, nu=self.nu, device=self.device)
+        return float(np.asarray(got).reshape(-1)[-1])
+
+    def _value_and_gradient(self, x):
+        x = np.asarray(x, dtype=np.float64)
+        h = self.STEP * (1.0 + np.abs(x))
+        rows = np.tile(x, (7, 1))
+        for i in range(3):
+            rows[1 + 2 * i, i] += h[i]
+            rows[2 + 2 * i, i] -= h[i]
+        v = self.negative_log_likelihoods(rows)
+        # the spacing actually taken (x + h - (x - h) in floating point)
+        g = np.array([(v[1 + 2 * i] - v[2 + 2 * i]) / (rows[1 + 2 * i, i] - rows[2 + 2 * i, i]) for i in range(3)])
+        if not np.all(v < 1e10):
+            g = np.zeros(3)
+        return float(v[0]), g
+
+    def optimize(self):
+        fbar = gas_link_inverse(self.copula, self._static_theta())
+        grid = np.array([[fbar * (1.0 - b), a, b] for b in self.BETAS for a in self.ALPHAS])
+        nll = self.negative_log_likelihoods(grid)                           # one launch
+        static_nll = float(nll[0])                                          # beta = 0, alpha = 0
+        if not np.any(nll < 1e10):
+            raise ValueError("score-driven copula fit: the likelihood is not finite at any grid start "
+                             "(a NaN marginal, or a marginal density that is not positive)")
+        best_x, best_nll = grid[int(np.argmin(nll))].copy(), float(np.min(nll))
+        for j in np.argsort(nll, kind="stable")[:self.N_REFINE]:
+            if not nll[j] < 1e10:
+                continue
+            res = minimize(self._value_and_gradient, grid[j], jac=True, method="L-BFGS-B", bounds=list(self.BOUNDS),
+                           tol=self.tol, options={"maxiter": self.max_iter})
+            val = float(self.negative_log_likelihoods(res.x[None, :])[0])
+            if val < best_nll:
+                best_x, best_nll = np.asarray(res.x, dtype=np.float64).copy(), val
+        return {"omega": float(best_x[0]), "alpha": float(best_x[1]), "beta": float(best_x[2]), "nll": best_nll,
+                "static_nll": static_nll, "static_theta": float(gas_link(self.copula, fbar)), "f_bar": fbar,
+                "launches": self.launches, "evaluations": self.evaluations,
+                "optimized_params": best_x}

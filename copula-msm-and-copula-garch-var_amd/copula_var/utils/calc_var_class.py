@@ -294,6 +294,16 @@ class ValueAtRiskCalcualtion:
         return rolling_copula_params(self.VaRCalculationMethod.copula_kind, self.marginals, self.densities, u, pdf,
                                      window, every, static_params=self.copula_params, device=self.device)
 
+    def gas_copula_params(self, fit=None):
+        """(params (T, n), info): this run's copula parameter on every out-of-sample date from the
+        score-driven recursion fitted once on the in-sample marginals and filtered through the
+        out-of-sample PITs before each date (copula_var.dynamic.gas_copula_params); a Student nu
+        stays the run's."""
+        from ..dynamic import gas_copula_params
+        u, _ = self.oos_pits()
+        return gas_copula_params(self.VaRCalculationMethod.copula_kind, self.marginals, u, self.copula_params, fit=fit,
+                                 device=self.device, in_sample_densities=self.densities)
+
     def _asset_index(self, asset) -> int:
         if isinstance(asset, str):
             tickers = list(self.tickers)

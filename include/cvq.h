@@ -543,6 +543,43 @@ int32_t cvq_ukf_filter(int32_t device, const double* params, int64_t B, const do
 int32_t cvq_garch_loglik_pq(int32_t device, int32_t p, int32_t q, const double* params, int64_t B,
                             const double* returns, int64_t N, double* out, int32_t mem);
 
+/* ------------------------------------- score-driven time-varying copula */
+/* No reference counterpart.  The observation-driven (GAS; Creal, Koopman and Lucas 2013) dependence
+ * recursion that produces the per-date copula parameters cvq_dynamic_quantiles and
+ * cvq_dynamic_distribution take (DESIGN.md §4 "Score-driven copula").  For rows u_t in (0,1)^dim,
+ * t = 0 .. N-1, and a candidate (omega, alpha, beta):
+ *     f_0 = omega / (1 - beta),   theta_t = link(f_t),   l_t = log c(u_t; theta_t),
+ *     s_t = d l_t / d f (analytic, unit scaling),   f_{t+1} = clamp(omega + beta f_t + alpha s_t, -40, 40).
+ * Links, sigma(f) = 1 / (1 + e^-f), inside the ranges the plans accept:
+ *     Gaussian, Student (nu fixed)   rho   = 0.99 (2 sigma(f) - 1)                  dim 2
+ *     Plackett                       theta = 0.1 * 10^(4 sigma(f))                  dim 2
+ *     Gumbel, Joe and rotations      theta = 1.0001 + (16 - 1.0001) sigma(f)        dim 2, 3
+ *     Frank                          theta = 1e-3 + (32 - 1e-3) sigma(f)            dim 2, 3
+ * copula: the CVQ_* kinds above.  The rotation follows cvq_static: CVQ_GUMBEL_SURVIVAL and
+ * CVQ_JOE_SURVIVAL are kinds of their own; `survival` != 0 with CVQ_GUMBEL / CVQ_JOE selects the same
+ * rotation (it is ignored with the two _SURVIVAL codes and CVQ_ERR_INVALID with any other kind).
+ * nu: the Student degrees of freedom (read for CVQ_STUDENT only).
+ * cvq_gas_loglik: ll_out[b] = sum_t l_t of candidate row b, one launch for all B rows; a row's
+ *   result does not depend on B or on the other rows (fixed-order sum, no atomics).
+ * cvq_gas_path: theta_out[0 .. N] (theta_t depends on the rows before t only; theta_N is the
+ *   one-step-ahead forecast) and, unless NULL, logc_out[t] = l_t.
+ * A candidate with |beta| >= 1 or a non-finite parameter, or whose f, s or l stops being finite at
+ * some row, is not an error: its ll is NaN; its logc is NaN from that row and its theta from the
+ * next one on.  params is host memory; u [N][dim] and the outputs are host|device per `mem`
+ * (the call returns after the device has finished in both modes).
+ * Validated on the host before any device work, outputs unwritten on failure:
+ *   CVQ_ERR_INVALID: a NULL pointer (logc_out may be NULL); B < 1 or N < 1; dim outside 2..3; Student
+ *     nu <= 0 or not finite; with host u, a value not strictly inside (0, 1) or NaN -- the message
+ *     names the first such row ("at row <i>");
+ *   CVQ_ERR_UNSUPPORTED: Gaussian, Student or Plackett with dim 3 (a correlation-matrix recursion is
+ *     not built); an unknown kind. */
+int32_t cvq_gas_loglik(int32_t device, int32_t copula, int32_t survival, int32_t dim, double nu,
+                       const double* params /*[B][3] = (omega, alpha, beta)*/, int64_t B,
+                       const double* u /*[N][dim]*/, int64_t N, double* ll_out /*[B]*/, int32_t mem);
+int32_t cvq_gas_path(int32_t device, int32_t copula, int32_t survival, int32_t dim, double nu,
+                     const double* params /*[3]*/, const double* u, int64_t N,
+                     double* theta_out /*[N+1]*/, double* logc_out /*[N] or NULL*/, int32_t mem);
+
 /* Special functions on the device (known-answer tests against scipy):
  * fn 0 = t.ppf(u, nu) (student.py:102), 1 = norm.ppf (gaussian.py:44),
  * 2 = erf (utils/utils.py:20), 3 = t.ppf as the solve kernels' tables evaluate it for
